@@ -2,7 +2,8 @@
 """bench.py -- fMRI volumes/sec through the full VAE-GAM train step on MI355X.
 
 Contract (driver): `python bench.py --gpus N --steps K --warmup W`; for N > 1 it is launched by
-torch.distributed.run with one rank per GPU.  Prints ONE JSON line on rank 0.
+torch.distributed.run with one rank per GPU.  Prints ONE JSON line on rank 0.  `--dump-outputs DIR` also writes
+what the last timed step computed as .npy files (the inputs are seeded: two builds can be compared output for output).
 
 Workload (`config.workload`): BASELINE.json configs[2], the largest single-GPU configuration -- the full
 VAE-GAM (GP regressors, HRF on `task`, GLM least-squares regulariser on) on the synthetic checker-control
@@ -37,6 +38,7 @@ FP32_PEAK_TF = 157.3
 ALG_BYTES_PER_VOL = {3: 69.6e6, 8: 139.2e6, 12: 194.8e6}
 ALG_GFLOP_PER_VOL = {3: 1.600, 8: 3.241, 12: 4.555}
 HIRES_ALG_BYTES_PER_VOL, HIRES_ALG_GFLOP_PER_VOL = 1739e6, 51.40   # 82x98x70, 12 covariates
+DUMP_BUDGET_BYTES, DUMP_SAMPLE_ELEMS = 64 << 20, 1 << 20            # --dump-outputs
 
 
 def host_threads():
@@ -109,11 +111,38 @@ def alg_bytes_per_launch(key, model, B):
     return None
 
 
+def dump_outputs(out_dir, loss, model):
+    """--dump-outputs: the loss one train step returns and the model state it leaves to its caller (the parameters after the
+    Adam update and the step's gradients), as <name>.npy in float32 / float64.  Over DUMP_BUDGET_BYTES (the 82x98x70 model's
+    fully connected weights), arrays above DUMP_SAMPLE_ELEMS elements keep a fixed sample: the same flat indices, seeded by
+    the array's name, in every run."""
+    import zlib
+    import numpy as np
+    import torch
+    arrays = [('loss', loss)]
+    for n, p in model.named_parameters():
+        arrays.append(('param.' + n, p.detach()))
+        if p.grad is not None:
+            arrays.append(('grad.' + n, p.grad.detach()))
+    arrays = [(n, t.cpu().numpy().astype(np.float64 if t.dtype == torch.float64 else np.float32)) for n, t in arrays]
+    if sum(v.nbytes for _, v in arrays) > DUMP_BUDGET_BYTES:
+        def sample(name, v):
+            rng = np.random.default_rng(zlib.crc32(name.split('.', 1)[-1].encode()))   # param.X and grad.X: the same indices
+            return np.ascontiguousarray(v.reshape(-1)[np.sort(rng.choice(v.size, DUMP_SAMPLE_ELEMS, replace=False))])
+        arrays = [(n, sample(n, v) if v.size > DUMP_SAMPLE_ELEMS else v) for n, v in arrays]
+    total = sum(v.nbytes for _, v in arrays)
+    assert total <= DUMP_BUDGET_BYTES, ('--dump-outputs: %d bytes after sampling' % total)
+    os.makedirs(out_dir, exist_ok=True)
+    for n, v in arrays:
+        np.save(os.path.join(out_dir, n + '.npy'), v)
+    print('[dump-outputs] %d arrays, %.1f MB -> %s' % (len(arrays), total / 2 ** 20, out_dir), file=sys.stderr)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
-    ap.add_argument('--steps', type=int, default=30)
-    ap.add_argument('--warmup', type=int, default=5)
+    ap.add_argument('--steps', type=int, default=None, help='timed steps (default 30; --hires: 10)')
+    ap.add_argument('--warmup', type=int, default=None, help='untimed steps before them (default 5; --hires: 3)')
     ap.add_argument('--batch', type=int, default=64, help='minibatch per GPU (configs[2]: 64; configs[1]: 32)')
     ap.add_argument('--covariates', type=int, default=8, help='configs[2]: 8 (full model); configs[1]: 3')
     ap.add_argument('--subjects', type=int, default=2)
@@ -123,7 +152,18 @@ def main():
     ap.add_argument('--kernel-table', action='store_true', help='print the per-kernel HIP-event table to stderr')
     ap.add_argument('--hires', action='store_true', help="BASELINE configs[4]'s per-GPU slice: 82x98x70 volumes, 12 covariates, 64 GP inducing points "
                     '(gp_jitter 1e-4, SURVEY H2), batch 64 per GPU; --batch / --steps as given (defaults here: 64, 10 steps after 3 warm-ups)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last timed step handed back (loss.npy, param.<name>.npy = the parameters '
+                         'after its Adam update, grad.<name>.npy = its gradients) under DIR, float32 / float64; when all of it exceeds '
+                         '%d MB, every array above %d elements is cut to a fixed seeded sample of that many (flat, sorted indices)'
+                         % (DUMP_BUDGET_BYTES >> 20, DUMP_SAMPLE_ELEMS))
     a = ap.parse_args()
+    if a.steps is None:
+        a.steps = 10 if a.hires else 30          # hi-res: 64 volumes of 82x98x70 x 13 decoder passes, ~0.14 s per step
+    if a.warmup is None:
+        a.warmup = 3 if a.hires else 5
+    if a.steps < 1 or a.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
 
     import numpy as np
     import torch
@@ -150,8 +190,6 @@ def main():
 
     if a.hires:
         a.covariates = 12
-        if a.steps == 30 and a.warmup == 5:
-            a.steps, a.warmup = 10, 3                                    # 64 volumes of 82x98x70 x 13 decoder passes: ~0.14 s per step
     B, C = a.batch, a.covariates
     # weak scaling: 2 synthetic subjects per GPU (configs[3]: 16 subjects on 8 GPUs), and always at least two global minibatches
     a.subjects = max(a.subjects, 2 * world)
@@ -170,9 +208,11 @@ def main():
     torch.manual_seed(1234 + 0)                                      # identical device noise stream on every rank
 
     def run_steps(n, first=0):
+        loss = None
         for s in range(first, first + n):
             smp = batches[s % len(batches)]
-            model.train_step(smp['subjid'], smp['covariates'], smp['volume'])
+            loss = model.train_step(smp['subjid'], smp['covariates'], smp['volume'])
+        return loss
 
     def barrier():
         if dp is not None:
@@ -188,9 +228,11 @@ def main():
     if not graphed:
         ops.PROFILE = {}                                             # HIP events on the launch stream, timed region
     t0 = time.perf_counter()
-    run_steps(a.steps, a.warmup)
+    last_loss = run_steps(a.steps, a.warmup)
     torch.cuda.synchronize(); barrier(); torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    if a.dump_outputs and rank == 0:                                 # before the per-kernel pass below moves the parameters on
+        dump_outputs(a.dump_outputs, last_loss, model)
     if graphed:
         # events cannot be recorded inside a replayed graph: time the same launches, same stream, eagerly,
         # right after the timed region (the kernels and their arguments are identical)

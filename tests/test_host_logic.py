@@ -450,3 +450,31 @@ def test_real_data_input_path_matches_the_reference_scripts(tmp_path):
     np.testing.assert_allclose(back[['task', 'x', 'y', 'z', 'rot_x', 'rot_y', 'rot_z', 'sex']].to_numpy(np.float64), g['csv.values'], rtol=1e-10, atol=1e-12)
     # what the data loader and the model then read from these two files
     assert len(utils.get_xu_ranges([csv, csv])) == 6
+
+
+def test_bench_dump_outputs_samples_large_models_the_same_way_every_run(tmp_path):
+    """bench.py --dump-outputs at the 82x98x70 model (--hires), whose parameters and gradients exceed the 64 MB budget: the
+    arrays above the sample size keep the same seeded flat indices in every run, param.X and grad.X alike; the rest is whole."""
+    import bench
+    img = (82, 98, 70)
+    ds = synthetic.make_dataset(num_subjects=1, vols_per_subject=2, num_covariates=12, seed=0, img_shape=img)
+    torch.manual_seed(1)
+    model = VAE(num_covariates=12, glm_maps=ds['glm'], xu_ranges=ds['xu_ranges'], device_name='cpu', img_shape=img,
+                num_inducing_pts=64, gp_jitter=1e-4)
+    for p in model.parameters():
+        p.grad.copy_(2 * p.detach())
+    for d in ('a', 'b'):
+        bench.dump_outputs(str(tmp_path / d), torch.tensor([1.5]), model)
+    files = sorted(os.listdir(tmp_path / 'a'))
+    assert files == sorted(os.listdir(tmp_path / 'b'))
+    assert sum(os.path.getsize(tmp_path / 'a' / f) for f in files) <= bench.DUMP_BUDGET_BYTES
+    assert np.load(tmp_path / 'a' / 'loss.npy').tolist() == [1.5]
+    for n, p in model.named_parameters():
+        pa, ga = np.load(tmp_path / 'a' / ('param.%s.npy' % n)), np.load(tmp_path / 'a' / ('grad.%s.npy' % n))
+        np.testing.assert_array_equal(pa, np.load(tmp_path / 'b' / ('param.%s.npy' % n)))
+        assert pa.dtype == (np.float64 if p.dtype == torch.float64 else np.float32)
+        np.testing.assert_array_equal(ga, 2 * pa)
+        if p.numel() > bench.DUMP_SAMPLE_ELEMS:
+            assert pa.shape == (bench.DUMP_SAMPLE_ELEMS,) and np.isin(pa, p.detach().numpy()).all()
+        else:
+            np.testing.assert_array_equal(pa, p.detach().numpy())

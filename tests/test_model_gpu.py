@@ -640,12 +640,13 @@ def test_device_prefetcher_yields_the_loaders_batches_on_the_device(tmp_path):
     assert losses[0] == losses[1]
 
 
-def test_bench_emits_the_contract_line():
+def test_bench_emits_the_contract_line(tmp_path):
     """bench.py (the driver's entry point): ONE JSON line on stdout with the metric, the roofline object of the dominant
-    kernel (HIP events on the launch stream) and the CPU baseline timed in the same run."""
+    kernel (HIP events on the launch stream) and the CPU baseline timed in the same run; --dump-outputs writes the arrays."""
     import subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--steps', '3', '--warmup', '2', '--cpu-steps', '1'],
+    r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--steps', '3', '--warmup', '2', '--cpu-steps', '1',
+                        '--dump-outputs', str(tmp_path / 'out')],
                        capture_output=True, text=True, timeout=600, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
@@ -662,3 +663,9 @@ def test_bench_emits_the_contract_line():
     cb = out['cpu_baseline']
     assert cb['kind'] == 'port' and cb['value'] > 0 and cb['cores'] >= 1 and 0 < cb['as_shipped_value'] <= cb['value']
     assert 'physical cores' in cb['sample']
+    # --dump-outputs: the last timed step's loss, parameters and gradients, one finite float32 / float64 array per name
+    names = sorted(os.listdir(tmp_path / 'out'))
+    assert 'loss.npy' in names and 'param.fc1.weight.npy' in names and 'grad.convt5.weight.npy' in names, names
+    for f in names:
+        v = np.load(tmp_path / 'out' / f)
+        assert v.dtype in (np.float32, np.float64) and v.size and np.isfinite(v).all(), f
