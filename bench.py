@@ -13,6 +13,11 @@ batch 64 PER GPU (weak scaling), random-init weights (seed 1), fp32, data reside
 A step = forward + backward + (N>1: RCCL all-reduce of the flat gradient buffer) + fused Adam on
 one minibatch.  `value` = N * batch * K / t, t = max over ranks of the barrier-bracketed wall time.
 
+A plain run does only that: set up, warm up, time the K steps, write --dump-outputs, print the line.  What takes runs of
+its own -- the per-kernel pass behind `roofline` and the CPU baseline -- runs only under `--full` (the per-kernel pass also
+under `--kernel-table`); in a plain run `roofline` is null unless the steps were launched eagerly (the events of the timed
+region then carry it), and `cpu_baseline` is null.
+
 roofline: the dominant kernel's ALGORITHMIC bytes (what it must read + write once, DESIGN.md
 "Kernels") / its mean duration, measured with HIP events recorded on the launching stream inside
 this run, against 8 TB/s; `traffic` = the PMC-measured HBM bytes per launch of that kernel from the
@@ -146,10 +151,13 @@ def main():
     ap.add_argument('--batch', type=int, default=64, help='minibatch per GPU (configs[2]: 64; configs[1]: 32)')
     ap.add_argument('--covariates', type=int, default=8, help='configs[2]: 8 (full model); configs[1]: 3')
     ap.add_argument('--subjects', type=int, default=2)
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--cpu-steps', type=int, default=5, help='timed CPU-oracle steps (median; after 2 warm-ups, SURVEY 8d); ~5 s each at batch 64 / 8 covariates on 16 threads')
+    ap.add_argument('--full', action='store_true', help='also measure what takes runs of its own: the per-kernel pass behind '
+                    '`roofline` (under hipGraph replay) and the CPU baseline (`cpu_baseline`); without it both are null '
+                    '(`roofline` unless --eager)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full without the CPU baseline')
+    ap.add_argument('--cpu-steps', type=int, default=5, help='--full: timed CPU-oracle steps (median; after 2 warm-ups, SURVEY 8d); ~5 s each at batch 64 / 8 covariates on 16 threads')
     ap.add_argument('--eager', action='store_true', help='launch kernels eagerly instead of replaying a captured hipGraph')
-    ap.add_argument('--kernel-table', action='store_true', help='print the per-kernel HIP-event table to stderr')
+    ap.add_argument('--kernel-table', action='store_true', help='print the per-kernel HIP-event table to stderr (runs the per-kernel pass, as --full does)')
     ap.add_argument('--hires', action='store_true', help="BASELINE configs[4]'s per-GPU slice: 82x98x70 volumes, 12 covariates, 64 GP inducing points "
                     '(gp_jitter 1e-4, SURVEY H2), batch 64 per GPU; --batch / --steps as given (defaults here: 64, 10 steps after 3 warm-ups)')
     ap.add_argument('--dump-outputs', metavar='DIR', default=None,
@@ -233,7 +241,8 @@ def main():
     dt = time.perf_counter() - t0
     if a.dump_outputs and rank == 0:                                 # before the per-kernel pass below moves the parameters on
         dump_outputs(a.dump_outputs, last_loss, model)
-    if graphed:
+    per_kernel = a.full or a.kernel_table
+    if graphed and per_kernel:
         # events cannot be recorded inside a replayed graph: time the same launches, same stream, eagerly,
         # right after the timed region (the kernels and their arguments are identical)
         # The step overlaps two launch chains (parameter gradients and the gain block on a second stream): inside it a kernel's
@@ -247,7 +256,7 @@ def main():
         ops.PROFILE = {}
         run_steps(max(3, min(a.steps, 10)), a.warmup + a.steps)
         torch.cuda.synchronize()
-    prof, ops.PROFILE = ops.PROFILE, None
+    prof, ops.PROFILE = ops.PROFILE or {}, None                     # (empty: replayed steps and no per-kernel pass)
     prof_steps = a.steps if not graphed else max(3, min(a.steps, 10))
     if dp is not None:
         dt = dp.max_scalar(dt)
@@ -264,13 +273,14 @@ def main():
     # HBM bytes per launch from the committed rocprofv3 PMC passes (profiles/, tools/profile_summary.py): used only while the
     # kernel sources hash to what was profiled and the workload is the profiled one -- a stale figure is dropped, not shown
     traffic_tab, traffic_ok = {}, False
-    try:
-        cands = sorted(f for f in os.listdir(os.path.join(ROOT, 'profiles')) if f.endswith('_traffic_by_layer.json'))
-        traffic_tab = json.load(open(os.path.join(ROOT, 'profiles', cands[-1])))
-        meta = traffic_tab.get('_meta', {})
-        traffic_ok = (meta.get('kernel_source_sha') == kernel_source_sha() and meta.get('batch') == B and meta.get('covariates') == C and not a.hires)
-    except Exception:
-        pass
+    if rows:
+        try:
+            cands = sorted(f for f in os.listdir(os.path.join(ROOT, 'profiles')) if f.endswith('_traffic_by_layer.json'))
+            traffic_tab = json.load(open(os.path.join(ROOT, 'profiles', cands[-1])))
+            meta = traffic_tab.get('_meta', {})
+            traffic_ok = (meta.get('kernel_source_sha') == kernel_source_sha() and meta.get('batch') == B and meta.get('covariates') == C and not a.hires)
+        except Exception:
+            pass
     for tot, key, n in rows:
         ab = alg_bytes_per_launch(key, model, B)
         if ab is None:
@@ -293,7 +303,7 @@ def main():
         print('sum of HIP kernel time %.3f ms/step (events), wall %.3f ms/step (%s)' % (tsum / prof_steps, ms_per_step, 'hipGraph replay' if graphed else 'eager'), file=sys.stderr)
 
     cpu = None
-    if rank == 0 and world == 1 and not a.no_cpu_baseline and not a.hires:     # (hi-res: one CPU step is minutes; the 41x49x35 line carries the CPU baseline)
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline and not a.hires:     # (hi-res: one CPU step is minutes; the 41x49x35 line carries the CPU baseline)
         sys.path.insert(0, os.path.join(ROOT, 'oracle'))
         import bridge
         import vaegam_oracle as O

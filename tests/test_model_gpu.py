@@ -641,11 +641,12 @@ def test_device_prefetcher_yields_the_loaders_batches_on_the_device(tmp_path):
 
 
 def test_bench_emits_the_contract_line(tmp_path):
-    """bench.py (the driver's entry point): ONE JSON line on stdout with the metric, the roofline object of the dominant
-    kernel (HIP events on the launch stream) and the CPU baseline timed in the same run; --dump-outputs writes the arrays."""
+    """bench.py --full (the driver's entry point with every leg on): ONE JSON line on stdout with the metric, the roofline
+    object of the dominant kernel (HIP events on the launch stream) and the CPU baseline timed in the same run; --dump-outputs
+    writes the arrays."""
     import subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--steps', '3', '--warmup', '2', '--cpu-steps', '1',
+    r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--full', '--steps', '3', '--warmup', '2', '--cpu-steps', '1',
                         '--dump-outputs', str(tmp_path / 'out')],
                        capture_output=True, text=True, timeout=600, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -669,3 +670,29 @@ def test_bench_emits_the_contract_line(tmp_path):
     for f in names:
         v = np.load(tmp_path / 'out' / f)
         assert v.dtype in (np.float32, np.float64) and v.size and np.isfinite(v).all(), f
+
+
+def test_plain_bench_run_times_the_steps_alone_and_computes_what_full_does(tmp_path):
+    """bench.py without --full: the same contract line with `roofline` and `cpu_baseline` null (no per-kernel pass, no CPU
+    baseline), and --dump-outputs writes, bit for bit, the arrays a --full run of the same steps writes."""
+    import subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    outs = {}
+    for name, extra in (('plain', []), ('full', ['--full', '--no-cpu-baseline'])):
+        r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--steps', '3', '--warmup', '2',
+                            '--dump-outputs', str(tmp_path / name)] + extra, capture_output=True, text=True, timeout=600, cwd=root)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [l for l in r.stdout.splitlines() if l.strip()]
+        assert len(lines) == 1, r.stdout
+        outs[name] = json.loads(lines[0])
+    plain, full = outs['plain'], outs['full']
+    assert sorted(plain) == sorted(full)
+    for k in ('metric', 'unit', 'higher_is_better', 'dtype', 'n_gpus', 'steps', 'warmup', 'config'):
+        assert plain[k] == full[k], k
+    assert plain['value'] > 1000 and plain['ms_per_step'] > 0 and 'hipGraph replay' in plain['config']['workload']
+    assert plain['roofline'] is None and plain['cpu_baseline'] is None
+    assert full['roofline']['bound'] == 'hbm' and full['cpu_baseline'] is None
+    names = sorted(os.listdir(tmp_path / 'plain'))
+    assert names == sorted(os.listdir(tmp_path / 'full')) and 'loss.npy' in names
+    for f in names:
+        np.testing.assert_array_equal(np.load(tmp_path / 'plain' / f), np.load(tmp_path / 'full' / f), err_msg=f)

@@ -4,7 +4,7 @@
 # group: FETCH_SIZE, WRITE_SIZE (cannot share a pass), the SQ matrix-core group, and the FETCH_SIZE calibration micro-benchmark.
 tag=${1:-round2}
 cd "$(dirname "$0")/.." && export TMPDIR=/tmp
-BENCH="bench.py --steps 10 --warmup 3 --no-cpu-baseline"
+BENCH="bench.py --full --steps 10 --warmup 3 --no-cpu-baseline"
 rm -rf gpurun_out/${tag}_stats gpurun_out/${tag}_stats_serial gpurun_out/${tag}_fetch gpurun_out/${tag}_write gpurun_out/${tag}_mfma gpurun_out/${tag}_calib
 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/${tag}_stats -o run -- python3 $BENCH > gpurun_out/${tag}_stats.log 2>&1 && echo "stats ok" &&
 VG_SIDE_STREAM=0 VG_OVERLAP_GAINS=0 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/${tag}_stats_serial -o run -- python3 $BENCH > gpurun_out/${tag}_stats_serial.log 2>&1 && echo "serial stats ok" &&

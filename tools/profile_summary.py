@@ -34,7 +34,7 @@ for sub, outname, how in (('stats_serial', '%s_kernel_stats_serial.csv', 'VG_SID
       rows = list(csv.DictReader(open(f)))
       tot = sum(float(r['TotalDurationNs']) for r in rows)
       with open(os.path.join(out_dir, outname % tag), 'w') as o:
-          o.write('# %srocprofv3 --kernel-trace --stats -- python3 bench.py --steps 10 --warmup 3 --no-cpu-baseline   (MI355X, BASELINE configs[2]: batch %d, %d covariates;\n' % (how, B, C))
+          o.write('# %srocprofv3 --kernel-trace --stats -- python3 bench.py --full --steps 10 --warmup 3 --no-cpu-baseline   (MI355X, BASELINE configs[2]: batch %d, %d covariates;\n' % (how, B, C))
           o.write('# 10 timed steps replayed from the hipGraph + warm-up/capture + one eager pass for the per-kernel HIP events)\n')
           o.write('Name,Calls,TotalDurationNs,AverageNs,Percentage,MinNs,MaxNs\n')
           for r in rows[:90]:
