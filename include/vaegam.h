@@ -239,6 +239,41 @@ int vg_loss_fwd(const float* kl, const float* slp, const float* dist, const floa
 int vg_loss_bwd(const float* g_loss, int32_t B, int32_t CB, double c_kl, double c_slp, double c_gp, double c_dist,
                 float* g_kl, float* g_slp, float* g_dist, float* g_gp, void* stream);
 
+/* Projection of the latent means (vae_reg_GP.py:542-583 project_latent, UMAP; host side: vae_gam_amd/latent_projection.py).
+ *
+ * Exact k nearest neighbours, Euclidean: x [N][D] fp32 row-major, 1 <= D <= 128, 1 <= k <= min(64, N) ->
+ *   idx [N][k] int32, dist [N][k] fp32.  Position 0 is the point itself at distance 0; positions 1..k-1 are the k-1 nearest
+ *   OTHER points sorted by (distance, index) ascending (ties go to the lower index).  distance = sqrtf(sum_d (x_i[d] - x_j[d])^2),
+ *   summed in fp32 over d = 0..D-1 in that order with fused multiply-adds (never the |a|^2 + |b|^2 - 2ab expansion).
+ *   ws: vg_knn_ws_bytes(N, D, k) bytes of device scratch (may be NULL when that is 0). */
+int64_t vg_knn_ws_bytes(int32_t N, int32_t D, int32_t k);
+int vg_knn(const float* x, int32_t N, int32_t D, int32_t k, void* ws, int32_t* idx, float* dist, void* stream);
+
+/* Fuzzy simplicial set of each neighbour row (umap-learn smooth_knn_dist + compute_membership_strengths, local_connectivity 1,
+ * bandwidth 1), in fp64: rho_i = smallest non-zero dist in row i (0 if none); sigma_i by at most 64 bisection steps to
+ * |sum_{j=1..k-1} f(d_ij - rho_i) - log2 k| < 1e-5 (f(t) = exp(-t/sigma) for t > 0, else 1; lo 0, hi inf, start 1, doubling while
+ * hi = inf), floored at 1e-3 * (mean of row i if rho_i > 0, else the mean of all N*k distances: a fixed-order reduction);
+ * w_ij = 0 for idx_ij = i, 1 if d_ij - rho_i <= 0 or sigma_i = 0, else exp(-(d_ij - rho_i)/sigma_i).
+ * dist, idx: vg_knn's output [N][k]; ws: 256 doubles of device scratch; rho, sigma [N], w [N][k] fp32. */
+int vg_umap_fuzzy(const float* dist, const int32_t* idx, int32_t N, int32_t k, double* ws, float* rho, float* sigma, float* w,
+                  void* stream);
+
+/* One synchronous (Jacobi) epoch of the 2-D UMAP layout: y_out = Y_{n+1} from y_in = Y_n ([N][2] fp32, distinct buffers).
+ * Graph: symmetric CSR rowptr [N+1], col [nnz], eps [nnz] = epochs_per_sample = max(W) / w_e.  For row i, entry e = (i, j) in CSR
+ * order, at epoch n = `epoch` (alpha = 1 - n/n_epochs in fp32):
+ *   due iff n >= 1 and floor(n/eps_e) > floor((n-1)/eps_e)  (in fp64);
+ *   attraction (d2 = |y_i - y_j|^2 > 0): c = -2ab d2^(b-1) / (a d2^b + 1); y_i += alpha*clip(c*(y_i - y_j), +-4), added TWICE (once as
+ *     head of (i, j), once as the other end of (j, i): W is symmetric, so (j, i) is due at the same epochs);
+ *   then negative_sample_rate (<= 31) samples s = 0, 1, ...: k = H mod N with
+ *     H = splitmix64_finaliser(((uint64)n << 44 | (uint64)e << 5 | s) + seed * 0x9E3779B97F4A7C15)   (all mod 2^64),
+ *     splitmix64_finaliser(z): z = (z ^ z>>30) * 0xBF58476D1CE4E5B9; z = (z ^ z>>27) * 0x94D049BB133111EB; z ^ z>>31;
+ *     skipped if k = i or d2 = |y_i - y_k|^2 = 0, else c = 2b / ((0.001 + d2)(a d2^b + 1)); y_i += alpha*clip(c*(y_i - y_k), +-4).
+ * All arithmetic fp32 (a, b rounded to fp32, powf), no fused multiply-adds; every contribution is added to y_i in the order listed.
+ * Limits: nnz < 2^39, n_epochs < 2^20, 0 <= epoch < n_epochs. */
+int vg_umap_layout_epoch(const int32_t* rowptr, const int32_t* col, const float* eps, const float* y_in, int32_t N, int32_t nnz,
+                         int32_t epoch, int32_t n_epochs, double a, double b, int32_t negative_sample_rate, uint64_t seed,
+                         float* y_out, void* stream);
+
 /* Fully connected layers (vae_reg_GP.py:197-210 fc1..fc8, :243-259 their use; replaces torch.nn.Linear / F.relu and what autograd
  * derives from them): one strided product on the matrix cores,
  *   C[z][m][n] (+)= epilogue( sum_k A[z](m,k) * B[z](k,n) ),   m < M, n < N, k < K, z < batch,

@@ -79,6 +79,10 @@ _PROTOS = {
     'vg_latent_bwd': (ctypes.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp]),
     'vg_loss_fwd': (ctypes.c_int, [vp, vp, vp, vp, i32, i32, f64, f64, f64, f64, vp, vp]),
     'vg_loss_bwd': (ctypes.c_int, [vp, i32, i32, f64, f64, f64, f64, vp, vp, vp, vp, vp]),
+    'vg_knn_ws_bytes': (i64, [i32, i32, i32]),
+    'vg_knn': (ctypes.c_int, [vp, i32, i32, i32, vp, vp, vp, vp]),
+    'vg_umap_fuzzy': (ctypes.c_int, [vp, vp, i32, i32, vp, vp, vp, vp, vp]),
+    'vg_umap_layout_epoch': (ctypes.c_int, [vp, vp, vp, vp, i32, i32, i32, i32, f64, f64, i32, ctypes.c_uint64, vp, vp]),
     'vg_channel_sum': (ctypes.c_int, [vp, i32, i32, i64, vp, vp, i32, vp]),
     'vg_gam_ws_bytes': (i64, [i32, i32, i64]),
     'vg_gam_elbo_fwd': (ctypes.c_int, [vp, vp, vp, vp, vp, i32, i32, i64, vp, vp, vp, vp, vp]),

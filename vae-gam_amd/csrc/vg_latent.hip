@@ -147,3 +147,302 @@ extern "C" int vg_loss_bwd(const float* g_loss, int32_t B, int32_t CB, double c_
               (float)c_gp, (float)c_dist, g_kl, g_slp, g_dist, g_gp);
     return vg_check_launch("loss_bwd");
 }
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// Projection of the latent means (vae_reg_GP.py:542-583 project_latent: UMAP, n_neighbors 20, min_dist 0.1, Euclidean): the exact
+// k-nearest-neighbour graph, the fuzzy simplicial set of each neighbour list and one synchronous SGD epoch of the 2-D layout.  The
+// host side (graph union, spectral init, the epoch loop) is vae_gam_amd/latent_projection.py.  None of this runs in the train step.
+#include <climits>
+#include <math.h>
+
+namespace {
+
+constexpr int KNN_Q = 256;      // queries per block, one per thread
+constexpr int KNN_TC = 16;      // candidates per LDS tile
+constexpr int KNN_DC = 16;      // dimensions per register chunk (D is zero-padded to a multiple of it; (0-0)^2 adds exactly 0)
+
+// a (distance, index) pair as one unsigned 64-bit key: a distance is >= 0 (or +inf), so its bit pattern orders like its value, and
+// ordering the keys orders by distance, then by index
+__device__ __forceinline__ uint64_t knn_key(float d, int j) {
+    union { float f; uint32_t u; } t; t.f = d;
+    return ((uint64_t)t.u << 32) | (uint32_t)j;
+}
+__device__ __forceinline__ float knn_key_dist(uint64_t k) { union { float f; uint32_t u; } t; t.u = (uint32_t)(k >> 32); return t.f; }
+__device__ __forceinline__ int knn_key_idx(uint64_t k) { return (int)(uint32_t)k; }
+constexpr uint64_t KNN_NONE = ~0ull;
+
+// sorted key list in registers, insertion by shifting the larger entries down one place: every index is a compile-time constant
+// (nothing goes to scratch).  The branch is taken by the whole wave when any lane inserts and the chain inside is branchless.
+// Call from wave-uniform control flow only.
+template <int KB>
+__device__ __forceinline__ void knn_insert(uint64_t (&kl)[KB], uint64_t key, bool valid) {
+    bool go = valid && key < kl[KB - 1];                 // key belongs at or above position m
+    if (!vg_any(go)) return;
+#pragma unroll
+    for (int m = KB - 1; m > 0; --m) {
+        const bool up = go && key < kl[m - 1];
+        kl[m] = up ? kl[m - 1] : (go ? key : kl[m]);
+        go = up;
+    }
+    kl[0] = go ? key : kl[0];
+}
+
+// block (query tile, candidate split): the K1 = k-1 nearest OTHER points of each query among candidates [c0, c1), written to
+// ws_d / ws_i [split][K1][N] (unfilled entries: distance NaN-bits, index -1, never inserted by the merge).  Candidate tiles of KNN_TC x Dp floats are staged in LDS and read
+// as broadcasts; a query accumulates sum (q-c)^2 over d = 0..D-1 in that order for KNN_TC candidates at a time.
+template <int KB>
+__global__ void __launch_bounds__(256)
+knn_partial_k(const float* __restrict__ x, int N, int D, int Dp, int K1, int chunk, float* __restrict__ ws_d, int* __restrict__ ws_i) {
+    VG_DYN_SMEM(float, tile);                            // [KNN_TC][Dp] candidates, then [KNN_TC][KNN_Q] this tile's distances
+    const int tid = threadIdx.x, q = blockIdx.x * KNN_Q + tid, split = blockIdx.y;
+    float* tdist = tile + KNN_TC * Dp;                   // each thread reads back only what it wrote: no barrier needed
+    const int c0 = split * chunk, c1 = min(N, c0 + chunk);
+    uint64_t kl[KB];
+#pragma unroll
+    for (int m = 0; m < KB; ++m) kl[m] = KNN_NONE;
+    const float* xq = x + (size_t)min(q, N - 1) * D;
+    for (int t0 = c0; t0 < c1; t0 += KNN_TC) {
+        __syncthreads();
+        for (int e = tid; e < KNN_TC * Dp; e += blockDim.x) {
+            const int c = e / Dp, d = e - c * Dp, j = t0 + c;
+            tile[e] = (j < c1 && d < D) ? x[(size_t)j * D + d] : 0.f;
+        }
+        __syncthreads();
+        float acc[KNN_TC];
+#pragma unroll
+        for (int c = 0; c < KNN_TC; ++c) acc[c] = 0.f;
+        for (int d0 = 0; d0 < Dp; d0 += KNN_DC) {
+            float qv[KNN_DC];
+#pragma unroll
+            for (int d = 0; d < KNN_DC; ++d) qv[d] = (d0 + d < D) ? xq[d0 + d] : 0.f;
+#pragma unroll
+            for (int c = 0; c < KNN_TC; ++c) {
+                const float* row = tile + c * Dp + d0;
+#pragma unroll
+                for (int d = 0; d < KNN_DC; d += 4) {
+                    const float4 v = *reinterpret_cast<const float4*>(row + d);
+                    float t;
+                    t = qv[d] - v.x; acc[c] = fmaf(t, t, acc[c]);
+                    t = qv[d + 1] - v.y; acc[c] = fmaf(t, t, acc[c]);
+                    t = qv[d + 2] - v.z; acc[c] = fmaf(t, t, acc[c]);
+                    t = qv[d + 3] - v.w; acc[c] = fmaf(t, t, acc[c]);
+                }
+            }
+        }
+#pragma unroll
+        for (int c = 0; c < KNN_TC; ++c) tdist[c * KNN_Q + tid] = sqrtf(acc[c]);
+#pragma unroll 1
+        for (int c = 0; c < KNN_TC; ++c) {             // one copy of the insertion code, not KNN_TC
+            const int j = t0 + c;
+            knn_insert(kl, knn_key(tdist[c * KNN_Q + tid], j), j < c1 && j != q);
+        }
+    }
+    if (q >= N) return;
+#pragma unroll
+    for (int m = 0; m < KB; ++m)
+        if (m < K1) { const size_t o = ((size_t)split * K1 + m) * N + q; ws_d[o] = knn_key_dist(kl[m]); ws_i[o] = knn_key_idx(kl[m]); }
+}
+
+// merge the S partial lists of each query; position 0 is the query itself at distance 0
+template <int KB>
+__global__ void __launch_bounds__(256)
+knn_merge_k(const float* __restrict__ ws_d, const int* __restrict__ ws_i, int N, int K1, int S, int32_t* __restrict__ idx,
+            float* __restrict__ dist) {
+    const int q = blockIdx.x * blockDim.x + threadIdx.x;
+    uint64_t kl[KB];
+#pragma unroll
+    for (int m = 0; m < KB; ++m) kl[m] = KNN_NONE;
+#pragma unroll 1
+    for (int s = 0; s < S; ++s)
+#pragma unroll 1
+        for (int m = 0; m < K1; ++m) { const size_t o = ((size_t)s * K1 + m) * N + min(q, N - 1); knn_insert(kl, knn_key(ws_d[o], ws_i[o]), q < N); }
+    if (q >= N) return;
+    const size_t r = (size_t)q * (K1 + 1);
+    idx[r] = q; dist[r] = 0.f;
+#pragma unroll
+    for (int m = 0; m < KB; ++m)
+        if (m < K1) { idx[r + 1 + m] = knn_key_idx(kl[m]); dist[r + 1 + m] = knn_key_dist(kl[m]); }
+}
+
+template <int KB>
+void knn_launch(const float* x, int N, int D, int K1, float* ws_d, int* ws_i, int S, int chunk, int32_t* idx, float* dist, hipStream_t s) {
+    const int Dp = vg_cdiv(D, KNN_DC) * KNN_DC;
+    if (K1 > 0)
+        vg_launch(knn_partial_k<KB>, dim3(vg_cdiv(N, KNN_Q), S), dim3(KNN_Q), (size_t)KNN_TC * (Dp + KNN_Q) * sizeof(float), s, x, N, D, Dp, K1,
+                  chunk, ws_d, ws_i);
+    vg_launch(knn_merge_k<KB>, dim3(vg_cdiv(N, 256)), dim3(256), 0, s, (const float*)ws_d, (const int*)ws_i, N, K1, S, idx, dist);
+}
+
+// candidate splits: enough blocks to fill the CUs at large N (~2048), at least 128 candidates per split, at most 16 splits
+void knn_splits(int N, int* S, int* chunk) {
+    const int qt = vg_cdiv(N, KNN_Q);
+    int s = min(vg_cdiv(2048, qt), N / 128);
+    s = s < 1 ? 1 : (s > 16 ? 16 : s);
+    *chunk = vg_cdiv(vg_cdiv(N, s), KNN_TC) * KNN_TC;
+    *S = vg_cdiv(N, *chunk);
+}
+
+constexpr int FZ_PARTS = 256;   // blocks of the fixed-order global mean
+
+// partial sums of all N*k distances over FZ_PARTS contiguous segments, each a fixed-order tree: deterministic
+__global__ void __launch_bounds__(256)
+umap_mean_part_k(const float* __restrict__ dist, int64_t n, double* __restrict__ part) {
+    __shared__ double red[256];
+    const int tid = threadIdx.x;
+    const int64_t seg = (n + FZ_PARTS - 1) / FZ_PARTS, b0 = blockIdx.x * seg, b1 = min(n, b0 + seg);
+    double s = 0.0;
+    for (int64_t i = b0 + tid; i < b1; i += blockDim.x) s += (double)dist[i];
+    red[tid] = s;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if (tid < w) red[tid] += red[tid + w];
+        __syncthreads();
+    }
+    if (tid == 0) part[blockIdx.x] = red[0];
+}
+
+// rho, sigma (binary search to |psum - log2 k| < 1e-5) and memberships of one neighbour row per thread, in fp64
+// (local_connectivity = 1, bandwidth = 1: umap-learn's smooth_knn_dist + compute_membership_strengths)
+__global__ void __launch_bounds__(256)
+umap_fuzzy_k(const float* __restrict__ dist, const int32_t* __restrict__ idx, int N, int k, const double* __restrict__ part,
+             float* __restrict__ rho, float* __restrict__ sigma, float* __restrict__ w) {
+    __shared__ double red[FZ_PARTS];
+    const int tid = threadIdx.x;
+    red[tid] = part[tid];
+    __syncthreads();
+    for (int h = 128; h > 0; h >>= 1) {
+        if (tid < h) red[tid] += red[tid + h];
+        __syncthreads();
+    }
+    const double mean_all = red[0] / ((double)N * k);
+    const int i = blockIdx.x * blockDim.x + tid;
+    if (i >= N) return;
+    const float* di = dist + (size_t)i * k;
+    double r = 0.0, rowsum = 0.0;
+    for (int j = 0; j < k; ++j) {
+        const double d = di[j];
+        rowsum += d;
+        if (d > 0.0 && (r == 0.0 || d < r)) r = d;
+    }
+    const double target = log2((double)k);
+    double lo = 0.0, hi = INFINITY, mid = 1.0;
+    for (int it = 0; it < 64; ++it) {
+        double psum = 0.0;
+        for (int j = 1; j < k; ++j) {
+            const double d = (double)di[j] - r;
+            psum += d > 0.0 ? exp(-(d / mid)) : 1.0;
+        }
+        if (fabs(psum - target) < 1e-5) break;
+        if (psum > target) { hi = mid; mid = (lo + hi) / 2.0; }
+        else { lo = mid; mid = (hi == INFINITY) ? mid * 2.0 : (lo + hi) / 2.0; }
+    }
+    const double floor_ = 1e-3 * (r > 0.0 ? rowsum / k : mean_all);
+    if (mid < floor_) mid = floor_;
+    rho[i] = (float)r; sigma[i] = (float)mid;
+    const int32_t* ii = idx + (size_t)i * k;
+    for (int j = 0; j < k; ++j) {
+        const double d = (double)di[j] - r;
+        w[(size_t)i * k + j] = ii[j] == i ? 0.f : ((d <= 0.0 || mid == 0.0) ? 1.f : (float)exp(-(d / mid)));
+    }
+}
+
+__device__ __forceinline__ uint64_t vg_splitmix64(uint64_t z) {
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+
+__device__ __forceinline__ float clip4(float v) { return v > 4.f ? 4.f : (v < -4.f ? -4.f : v); }
+
+// one synchronous epoch: thread i walks row i of the symmetric CSR graph, reads Y_n only and writes its own row of Y_{n+1}.  Every
+// contribution is added to y_i in CSR order, then sample order (no fused multiply-adds: the order and rounding are the documented ones).
+__global__ void __launch_bounds__(256)
+umap_layout_k(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col, const float* __restrict__ eps,
+              const float* __restrict__ yin, int N, int n, int n_epochs, float a, float b, int neg, uint64_t seed,
+              float* __restrict__ yout) {
+#pragma clang fp contract(off)
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= N) return;
+    const float alpha = 1.f - (float)n / (float)n_epochs;
+    const float yx = yin[2 * i], yy = yin[2 * i + 1];
+    float ox = yx, oy = yy;
+    const float two_ab = -2.f * a * b, bm1 = b - 1.f, two_b = 2.f * b;
+    const uint64_t sk = seed * 0x9E3779B97F4A7C15ull;
+    if (n >= 1) {
+        const int e1 = rowptr[i + 1];
+        for (int e = rowptr[i]; e < e1; ++e) {
+            const double ep = eps[e];
+            if (!(floor((double)n / ep) > floor((double)(n - 1) / ep))) continue;
+            const int j = col[e];
+            float dx = yx - yin[2 * j], dy = yy - yin[2 * j + 1];
+            float d2 = dx * dx + dy * dy;
+            if (d2 > 0.f) {
+                const float coef = (two_ab * powf(d2, bm1)) / (a * powf(d2, b) + 1.f);
+                const float gx = alpha * clip4(coef * dx), gy = alpha * clip4(coef * dy);
+                ox = ox + gx; oy = oy + gy;              // as head of (i, j)
+                ox = ox + gx; oy = oy + gy;              // as the other end of (j, i)
+            }
+            const uint64_t key = ((uint64_t)n << 44) | ((uint64_t)e << 5);
+            for (int s = 0; s < neg; ++s) {
+                const int kk = (int)(vg_splitmix64((key | (uint64_t)s) + sk) % (uint64_t)N);
+                if (kk == i) continue;
+                dx = yx - yin[2 * kk]; dy = yy - yin[2 * kk + 1];
+                d2 = dx * dx + dy * dy;
+                if (!(d2 > 0.f)) continue;
+                const float coef = two_b / ((0.001f + d2) * (a * powf(d2, b) + 1.f));
+                ox = ox + alpha * clip4(coef * dx); oy = oy + alpha * clip4(coef * dy);
+            }
+        }
+    }
+    yout[2 * i] = ox; yout[2 * i + 1] = oy;
+}
+
+}  // namespace
+
+extern "C" int64_t vg_knn_ws_bytes(int32_t N, int32_t D, int32_t k) {
+    if (N <= 0 || D < 1 || D > 128 || k < 1 || k > 64 || k > N) { vg_set_error("vg_knn_ws_bytes: bad shape (N %d, D %d, k %d)", N, D, k); return -1; }
+    int S, chunk;
+    knn_splits(N, &S, &chunk);
+    return (int64_t)S * (k - 1) * N * 8;
+}
+
+extern "C" int vg_knn(const float* x, int32_t N, int32_t D, int32_t k, void* ws, int32_t* idx, float* dist, void* stream) {
+    if (!x || !idx || !dist || (k > 1 && !ws)) { vg_set_error("vg_knn: null argument"); return VG_ERR_ARG; }
+    if (N <= 0 || D < 1 || D > 128 || k < 1 || k > 64 || k > N || (int64_t)N * k > INT_MAX) { vg_set_error("vg_knn: bad shape (N %d, D %d, k %d)", N, D, k); return VG_ERR_ARG; }
+    int S, chunk;
+    knn_splits(N, &S, &chunk);
+    const int K1 = k - 1;
+    float* ws_d = (float*)ws;
+    int* ws_i = ws ? (int*)((char*)ws + (size_t)S * K1 * N * 4) : nullptr;
+    hipStream_t s = (hipStream_t)stream;
+    if (K1 <= 8) knn_launch<8>(x, N, D, K1, ws_d, ws_i, S, chunk, idx, dist, s);
+    else if (K1 <= 16) knn_launch<16>(x, N, D, K1, ws_d, ws_i, S, chunk, idx, dist, s);
+    else if (K1 <= 32) knn_launch<32>(x, N, D, K1, ws_d, ws_i, S, chunk, idx, dist, s);
+    else knn_launch<64>(x, N, D, K1, ws_d, ws_i, S, chunk, idx, dist, s);
+    return vg_check_launch("knn");
+}
+
+extern "C" int vg_umap_fuzzy(const float* dist, const int32_t* idx, int32_t N, int32_t k, double* ws, float* rho, float* sigma,
+                             float* w, void* stream) {
+    if (!dist || !idx || !ws || !rho || !sigma || !w) { vg_set_error("vg_umap_fuzzy: null argument"); return VG_ERR_ARG; }
+    if (N <= 0 || k < 1 || k > 64 || (int64_t)N * k > INT_MAX) { vg_set_error("vg_umap_fuzzy: bad shape (N %d, k %d)", N, k); return VG_ERR_ARG; }
+    vg_launch(umap_mean_part_k, dim3(FZ_PARTS), dim3(256), 0, (hipStream_t)stream, dist, (int64_t)N * k, ws);
+    vg_launch(umap_fuzzy_k, dim3(vg_cdiv(N, 256)), dim3(256), 0, (hipStream_t)stream, dist, idx, (int)N, (int)k, (const double*)ws,
+              rho, sigma, w);
+    return vg_check_launch("umap_fuzzy");
+}
+
+extern "C" int vg_umap_layout_epoch(const int32_t* rowptr, const int32_t* col, const float* eps, const float* y_in, int32_t N,
+                                    int32_t nnz, int32_t epoch, int32_t n_epochs, double a, double b, int32_t negative_sample_rate,
+                                    uint64_t seed, float* y_out, void* stream) {
+    if (!rowptr || !y_in || !y_out || (nnz > 0 && (!col || !eps)) || y_in == y_out) { vg_set_error("vg_umap_layout_epoch: bad pointer argument"); return VG_ERR_ARG; }
+    if (N <= 0 || nnz < 0 || (int64_t)nnz >= ((int64_t)1 << 39) || n_epochs < 1 || n_epochs >= (1 << 20) || epoch < 0 || epoch >= n_epochs ||
+        negative_sample_rate < 0 || negative_sample_rate > 31) {
+        vg_set_error("vg_umap_layout_epoch: bad argument (N %d, nnz %d, epoch %d of %d, negative_sample_rate %d)", N, nnz, epoch, n_epochs,
+                     negative_sample_rate);
+        return VG_ERR_ARG;
+    }
+    vg_launch(umap_layout_k, dim3(vg_cdiv(N, 256)), dim3(256), 0, (hipStream_t)stream, rowptr, col, eps, y_in, (int)N, (int)epoch,
+              (int)n_epochs, (float)a, (float)b, (int)negative_sample_rate, seed, y_out);
+    return vg_check_launch("umap_layout_epoch");
+}

@@ -2,10 +2,10 @@
 multsubj_reg_run_GP.py:19-56; run as `python -m vae_gam_amd.multsubj_reg_run_GP ...`).
 
 After training -- or straight from a checkpoint with `--recons_only` -- the wrapper runs the reference's export pipeline
-(multsubj_reg_run_GP.py:79-92): `model.plot_GPs` (per-covariate GP posterior CSVs), `recon.mk_single_volumes` (one NIfTI
-per volume and map) and `recon.mk_avg_maps(mk_motion_maps=True)` (subject and grand averages), all on the training set as
-the reference does.  `project_latent` (a UMAP scatter plot of the latent means; umap-learn / plotting) is not part of the
-hot path and is skipped with a printed note.
+(multsubj_reg_run_GP.py:79-92): `model.project_latent` (UMAP projection of the latent means on the HIP kernels of
+latent_projection.py: `<epoch>_temp.pdf` and `<epoch>_latent_projection.csv`), `model.plot_GPs` (per-covariate GP posterior
+CSVs), `recon.mk_single_volumes` (one NIfTI per volume and map) and `recon.mk_avg_maps(mk_motion_maps=True)` (subject and
+grand averages), all on the training set as the reference does.
 
 Multi-GPU: launch with torch.distributed.run, one process per GPU; the wrapper picks up RANK / LOCAL_RANK / WORLD_SIZE,
 `--batch-size` stays the GLOBAL minibatch and every rank draws its own slice of it (dp.ShardedBatchSampler); checkpoints
@@ -32,7 +32,7 @@ def build_parser():
     parser.add_argument('--seed', type=int, default=1, metavar='S', help='Random seed (default: 1)')
     parser.add_argument('--save_freq', type=int, default=100, metavar='N', help='How many epochs to wait before saving training status.')
     parser.add_argument('--test_freq', type=int, default=200, metavar='N', help='How many epochs to wait before testing.')
-    parser.add_argument('--split', type=int, metavar='N', default=98, help='# of volumes per subject (latent plot colouring; kept for compatibility).')
+    parser.add_argument('--split', type=int, metavar='N', default=98, help='# of volumes per subject (one colour per chunk of this size in the latent projection plot).')
     parser.add_argument('--glm_reg_scale', type=float, metavar='N', default=1.0, help='Scaling factor for GLM map regularization term (default: 1)')
     parser.add_argument('--glm_maps', type=str, metavar='N', default='', help='Path to csv file containing matrix with approximate GLM maps.')
     parser.add_argument('--num_inducing_pts', type=int, metavar='N', default=6, help='Number of inducing points for each regressor 1D GP.')
@@ -104,7 +104,7 @@ def export_outputs(model, loaders_dict, args, dp=None):
             return
     saved_dp, model.dp = model.dp, None
     try:
-        print('project_latent (UMAP plot of the latent space, vae_reg_GP.py:542-583) is not part of this build: skipped.')
+        model.project_latent(loaders_dict, title="Latent Space plot", split=args.split, save_dir=args.save_dir)
         model.plot_GPs(csv_file=args.train_csv, save_dir=args.save_dir)
         recon.mk_single_volumes(loaders_dict['UnShuffled_train'], model, args.train_csv, args.save_dir)
         recon.mk_avg_maps(args.train_csv, model, args.save_dir, mk_motion_maps=True)

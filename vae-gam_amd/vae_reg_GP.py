@@ -841,6 +841,49 @@ class VAE(nn.Module):
             out[n] = df
         return out
 
+    def project_latent(self, loaders_dict, save_dir, title=None, split=98):
+        """Reference signature (vae_reg_GP.py:542-583): the latent means mu of every volume of loaders_dict['UnShuffled_train'],
+        encoded batch by batch as the reference does (batch-norm statistics depend on the batch), projected to 2-D by UMAP with the
+        reference's settings (n_neighbors 20, min_dist 0.1, random_state 42; latent_projection.umap_project on the HIP kernels) and
+        plotted to `<epoch>_temp.pdf`, one colour of the reference's 14-colour cycle per `split`-sized chunk.  Also writes
+        `<epoch>_latent_projection.csv` (subjid, vol_num, mu_0.., umap_0, umap_1: an extension, to re-plot without recomputing).
+        Returns (latent, projection) as ndarrays (the reference's commented-out return)."""
+        import itertools
+        import pandas as pd
+        from . import latent_projection
+        mus, subj, vols = [], [], []
+        with torch.no_grad():
+            for sample in loaders_dict['UnShuffled_train']:
+                mu, _, _ = self.encode(sample['volume'].to(self.device))
+                mus.append(mu.detach())
+                subj.append(sample['subjid'].reshape(-1).cpu().numpy().astype(np.int64))
+                vols.append(sample['vol_num'].reshape(-1).cpu().numpy().astype(np.int64))
+            latent_t = torch.cat(mus).to(torch.float32).contiguous()
+            proj_t = latent_projection.umap_project(latent_t, n_neighbors=20, min_dist=0.1, random_state=42)
+        latent, projection = latent_t.cpu().numpy(), proj_t.cpu().numpy()
+        os.makedirs(save_dir, exist_ok=True)
+        stem = os.path.join(save_dir, str(self.epoch).zfill(3))
+        cols = {'subjid': np.concatenate(subj), 'vol_num': np.concatenate(vols)}
+        cols.update({'mu_%d' % j: latent[:, j] for j in range(latent.shape[1])})
+        cols.update({'umap_0': projection[:, 0], 'umap_1': projection[:, 1]})
+        pd.DataFrame(cols).to_csv(stem + '_latent_projection.csv', index=False)
+        try:
+            from matplotlib.figure import Figure
+        except ImportError:
+            print('project_latent: matplotlib is not installed; %s_temp.pdf not written (the projection is in the CSV).' % stem)
+            return latent, projection
+        fig = Figure()
+        ax = fig.add_subplot(1, 1, 1)
+        colors = itertools.cycle(['b', 'g', 'r', 'c', 'm', 'y', 'k', 'orange', 'blueviolet', 'hotpink', 'lime', 'skyblue', 'teal',
+                                  'sienna'])
+        for i in range(0, len(projection), max(int(split), 1)):
+            ax.scatter(projection[i:i + split, 0], projection[i:i + split, 1], color=next(colors), s=1.0, alpha=0.6)
+        ax.axis('off')
+        if title is not None:
+            ax.set_title(title)
+        fig.savefig(stem + '_temp.pdf')
+        return latent, projection
+
     def reconstruct_batch(self, ids, covariates, x):
         """Maps of one batch as ndarrays keyed like the reference's `imgs` (vae_reg_GP.py:605)."""
         with torch.no_grad():
