@@ -325,7 +325,17 @@ int vg_cholesky_f64(const double* a, double* l, int32_t batch, int32_t n, void* 
  * covariance, its B x B Cholesky factor, the reparameterised gain sample, the HRF along the batch axis and both KL terms
  * (vae_reg_GP.py:345-378 with gp.py:41-110: gp.GP.evaluate_posterior -- kernel build {Knu, Knn, Ku}, Ku solve --,
  * compute_GP_kl, calc_linW_KL, MultivariateNormal(beta_mean, beta_cov + 1e-5 I).rsample(), do_hrf_conv), forward and backward,
- * one workgroup per covariate, float64 arithmetic on fp32 inputs.
+ * float64 arithmetic on fp32 inputs.
+ *   Batch ranges: 1 <= B <= 1024 one workgroup per covariate (B x B matrix in LDS up to 16, beyond that the blocked Cholesky and
+ *   slab solves with a panel / slab in LDS); 1024 < B <= 4096 the TILED path: the same arithmetic spread over at least
+ *   C * ceil(B / 64) workgroups per O(B^2) / O(B^3) launch (64 x 64 tiles, a blocked right-looking Cholesky of three launches per
+ *   64-column panel, left-looking slab solves); B > 4096 returns VG_ERR_UNSUPPORTED.  vg_gp_gain_fwd_tiled / _bwd_tiled take the
+ *   tiled path at any B >= 1 (same arguments, same workspace); a backward call must use the pair of its forward call.
+ *   Workspace: vg_gp_gain_ws_bytes = 8 (C (2 B^2 + 4 B n + 7 n^2 + 6 B + 16, rounded up to a multiple of 8) + C + 8) bytes, the same
+ *   layout on both paths (about 268 MB per covariate at B = 4096).
+ *   Determinism: every sum runs in a fixed order and no float atomics are used; both paths are run-to-run bit-reproducible and can
+ *   be captured in a hipGraph (no allocation, no host synchronisation, ordering by launch boundaries only).  The tiled path agrees
+ *   with the other to rounding, not bit for bit (different blocking of the same sums).
  *   table  [C][10] int64 (device): {is_gp, is_hrf, gp_index, off_sa, off_logstd, off_qu_m, off_qu_S, off_logkvar, off_log_ls, 0},
  *          offsets = element offsets of that covariate's parameters inside `params` (the flat fp32 parameter buffer);
  *   xu     [#gp][n] fp32 inducing grids (row gp_index);  covariates: element (b, i) at covariates[b*ld_cov + i], B rows (the GLOBAL
@@ -351,6 +361,12 @@ int vg_gp_gain_fwd(const vg_gain_desc* d, const int64_t* table, const float* par
 int vg_gp_gain_bwd(const vg_gain_desc* d, const int64_t* table, const float* params, const float* xu,
                    const float* covariates, int64_t ld_cov, const float* eps_beta, const double* hrf_taps, void* ws,
                    const float* g_task_var, const float* g_gp_kl, float* flat_grads, void* stream);
+int vg_gp_gain_fwd_tiled(const vg_gain_desc* d, const int64_t* table, const float* params, const float* xu,
+                         const float* covariates, int64_t ld_cov, const float* eps_beta, const double* hrf_taps, void* ws,
+                         float* task_var, float* gp_kl, double* beta_mean, double* beta_cov, double* f_bar, double* Sigma, void* stream);
+int vg_gp_gain_bwd_tiled(const vg_gain_desc* d, const int64_t* table, const float* params, const float* xu,
+                         const float* covariates, int64_t ld_cov, const float* eps_beta, const double* hrf_taps, void* ws,
+                         const float* g_task_var, const float* g_gp_kl, float* flat_grads, void* stream);
 
 /* fused Adam (torch.optim.Adam defaults, vae_reg_GP.py:179,429) over one flat buffer:
  * p,g,m,v: n elements of fp32 (is_f64 = 0) or fp64 (is_f64 = 1).  step_size = lr/(1-b1^t),

@@ -63,6 +63,7 @@ def main(argv=None):
     rank = 0 if dp is None else dp.rank
     if dp is not None and args.batch_size % dp.world_size:
         raise SystemExit('--batch-size %d (the GLOBAL minibatch) must be a multiple of the %d ranks' % (args.batch_size, dp.world_size))
+    check_batch_size(args.batch_size, 1 if dp is None else dp.world_size, os.environ.get('VG_DP_GAIN', 'global'))
     # the reference's loaders (whole data set, GLOBAL minibatch, multsubj_reg_run_GP.py:69): what the export pipeline iterates -- gains
     # (joint draw, HRF along the batch) and the decoder's batch statistics depend on the batch composition, so the exported maps must
     # see the batches a single process would; under data parallelism the train / test loops get re-built loaders that hand each rank
@@ -89,6 +90,19 @@ def main(argv=None):
     if rank == 0:
         print('Total model runtime (seconds): {}'.format(time.time() - main_start))
     return model
+
+
+def check_batch_size(batch_size, world_size=1, dp_gain='global'):
+    """Refuse, before any data is loaded, a --batch-size whose gains the gain block cannot draw jointly (ops.GAIN_MAX_BATCH): the
+    training step draws the global minibatch (dp_gain='global') or each rank's slice ('local'); the export pipeline always draws the
+    whole minibatch in one process."""
+    from . import ops
+    train = batch_size if dp_gain == 'global' else batch_size // max(1, world_size)
+    try:
+        ops.check_gain_batch(train, '--batch-size %d on %d rank(s) with dp_gain=%r' % (batch_size, world_size, dp_gain))
+        ops.check_gain_batch(batch_size, '--batch-size %d in the export pipeline (one process, whole minibatches)' % batch_size)
+    except ValueError as e:
+        raise SystemExit(str(e))
 
 
 def export_outputs(model, loaders_dict, args, dp=None):

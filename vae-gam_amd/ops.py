@@ -1000,6 +1000,20 @@ def cholesky(a):
     return torch.linalg.cholesky_ex(a, check_errors=False).L
 
 
+GAIN_MAX_BATCH = 4096          # volumes per joint gain draw (vg_gp_gain_*: B > 1024 takes the tiled path, B > 4096 is refused)
+# Tests only (set with monkeypatch): route every GpGain call through vg_gp_gain_fwd_tiled / _bwd_tiled, the tiled path at any B.
+# Off: the library picks the path by batch size.
+GAIN_FORCE_TILED = False
+
+
+def check_gain_batch(B, what='the gain block'):
+    """ValueError unless `B` volumes fit one joint gain draw (B <= GAIN_MAX_BATCH)."""
+    if int(B) > GAIN_MAX_BATCH:
+        raise ValueError('%s would draw the gains of %d volumes jointly: the limit is %d volumes per joint draw (vg_gp_gain_fwd). '
+                         'Use a smaller minibatch or, under data parallelism, dp_gain=\'local\' (each rank draws its own slice).'
+                         % (what, int(B), GAIN_MAX_BATCH))
+
+
 class GainConsts:
     """Device-side constants of the gain block of one model: the parameter-offset table, the inducing grids, the HRF taps."""
 
@@ -1015,7 +1029,8 @@ class GainConsts:
 class GpGain(torch.autograd.Function):
     """(covariates (B, >=C) fp32, eps_beta (C, B) fp32) -> gains task_var (C, B) fp32, gp_kl (1,) fp32 and float64 copies of
     beta_mean (C,B), beta_cov (C,B,B), f_bar (C,B), Sigma (C,B,B), kl terms (C,) for exports / tests: vg_gp_gain_fwd, one
-    workgroup per covariate (vae_reg_GP.py:345-378, gp.py:41-110).  The backward launch adds the gain-parameter gradients
+    workgroup per covariate up to B = 1024, the tiled multi-workgroup path up to B = 4096 (vae_reg_GP.py:345-378, gp.py:41-110;
+    GAIN_FORCE_TILED: the tiled path at any B).  The backward launch adds the gain-parameter gradients
     straight into the flat fp32 gradient buffer; `params` are listed only so that autograd calls it.
     `join_stream`: the stream that must wait for the backward launch (the model runs this block on a second stream)."""
 
@@ -1036,11 +1051,12 @@ class GpGain(torch.autograd.Function):
         bc = torch.empty((C, B, B), dtype=torch.float64, device=dev)
         fb = torch.zeros((C, B), dtype=torch.float64, device=dev)
         sg = torch.zeros((C, B, B), dtype=torch.float64, device=dev)
-        _call(covariates, 'vg_gp_gain_fwd', ctypes.byref(d), _p(consts.table), _p(flat_p), _p(consts.xu), _p(covariates),
+        tiled = bool(GAIN_FORCE_TILED)
+        _call(covariates, 'vg_gp_gain_fwd_tiled' if tiled else 'vg_gp_gain_fwd', ctypes.byref(d), _p(consts.table), _p(flat_p), _p(consts.xu), _p(covariates),
               int(covariates.stride(0)), _p(eps_beta), _p(consts.hrf), _p(ws), _p(tv), _p(kl), _p(bm), _p(bc), _p(fb), _p(sg))
         kl_terms = ws[-(C + 8):-8]                                # per-covariate kl_lin (+ kl_gp), float64
         ctx.save_for_backward(covariates, eps_beta, ws)
-        ctx.consts, ctx.flat_p, ctx.flat_g, ctx.join_stream = consts, flat_p, flat_g, join_stream
+        ctx.consts, ctx.flat_p, ctx.flat_g, ctx.join_stream, ctx.tiled = consts, flat_p, flat_g, join_stream, tiled
         ctx.mark_non_differentiable(bm, bc, fb, sg, kl_terms)
         return tv, kl, bm, bc, fb, sg, kl_terms
 
@@ -1055,7 +1071,7 @@ class GpGain(torch.autograd.Function):
         if g_kl is None:
             g_kl = torch.zeros(1, dtype=torch.float32, device=covariates.device)
         g_tv = _chk(g_tv.contiguous()); g_kl = _chk(g_kl.contiguous())
-        _call(covariates, 'vg_gp_gain_bwd', ctypes.byref(d), _p(consts.table), _p(ctx.flat_p), _p(consts.xu), _p(covariates),
+        _call(covariates, 'vg_gp_gain_bwd_tiled' if ctx.tiled else 'vg_gp_gain_bwd', ctypes.byref(d), _p(consts.table), _p(ctx.flat_p), _p(consts.xu), _p(covariates),
               int(covariates.stride(0)), _p(eps_beta), _p(consts.hrf), _p(ws), _p(g_tv), _p(g_kl), _p(ctx.flat_g))
         if ctx.join_stream is not None and covariates.is_cuda:
             cur = torch.cuda.current_stream(covariates.device)

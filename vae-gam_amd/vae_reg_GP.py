@@ -108,7 +108,10 @@ class VAE(nn.Module):
         'global' (default) = the gains of the whole global minibatch are drawn jointly on every rank from the dense Bg x Bg gain
         covariance (vae_reg_GP.py:363-369; covariates all-gathered, identical seeded noise, own columns kept): exactly the one-process
         global-batch step.  Its O(Bg^3) Cholesky / triangular solves run blocked on the matrix cores' neighbours (vg_gp.hip, large-batch
-        path): 0.5 + 0.7 ms at Bg = 256, 1.8 + 1.9 ms at 512, on a side stream beside the conv stacks.
+        path): 0.5 + 0.7 ms at Bg = 256, 1.8 + 1.9 ms at 512, on a side stream beside the conv stacks; above Bg = 1024 they
+        run on the tiled multi-workgroup path.  The joint draw takes at most 4,096 volumes (ops.GAIN_MAX_BATCH):
+        forward_core / train_step / reconstruct raise ValueError, before the first kernel launch of the step, for a larger batch than
+        that as the gain block sees it (the global batch under 'global', the rank's slice under 'local').
         'local' = every rank draws the gains of ITS slice from that slice's own B x B block -- the block-DIAGONAL approximation of
         the joint draw: gains of volumes on different ranks are drawn independently (their covariance through the GP is dropped),
         every volume's own marginal N(beta_mean_b, Sigma_bb) is unchanged; the HRF of the neural covariates still runs along the
@@ -443,6 +446,19 @@ class VAE(nn.Module):
         return self._glm_f32
 
     # ------------------------------------------------------------------ forward
+    def gain_batch(self, B):
+        """Volumes whose gains the block draws jointly when this rank holds a minibatch (slice) of B: the global batch under data
+        parallelism with dp_gain='global', else B."""
+        if self.dp is not None and self.dp_gain == 'global':
+            return int(B) * self.dp.world_size
+        return int(B)
+
+    def check_gain_batch(self, B):
+        """ValueError if the gain block cannot draw the gains of a (per-rank) minibatch of B volumes (ops.GAIN_MAX_BATCH = 4096
+        per joint draw)."""
+        ops.check_gain_batch(self.gain_batch(B), 'a minibatch of %d volumes per rank' % int(B) if self.dp is not None else
+                             'a minibatch of %d volumes' % int(B))
+
     def forward_core(self, covariates, x, noise=None, want_maps=False):
         """The arithmetic of VAE.forward (vae_reg_GP.py:307-410), on device, no host syncs.
         Returns a dict of device tensors: loss (1,), z, mu, u, d, kl_z, task_var (C,B), gp_kl_loss,
@@ -452,6 +468,7 @@ class VAE(nn.Module):
         x = x.float()
         covariates = covariates[:, :C].float()           # the loaders always carry the reference's 8 columns; covariate i reads column i-1 (:345)
         self._require_gpu(x)                         # before ANY launch: host pointers must never reach a kernel
+        self.check_gain_batch(B)                     # before ANY launch, too: the gain block's limit on the jointly drawn batch
         self._packed.refresh()                       # one launch: every conv weight -> the images the kernels read
         # data parallel: this rank holds rows [lo, lo+B) of a global batch of Bg = world*B volumes
         W, lo, Bg = 1, 0, B
@@ -556,6 +573,7 @@ class VAE(nn.Module):
         With `self.use_hip_graph` the whole step (zero-grad, forward, backward, gradient all-reduce,
         fused Adam: a few hundred launches) is captured once per batch shape into a hipGraph and
         replayed; the host then only copies the minibatch into the graph's input buffers."""
+        self.check_gain_batch(x.shape[0])
         if self.use_hip_graph and noise is None and x.is_cuda:
             g = self._graphs.get(tuple(x.shape))
             if g is None:
