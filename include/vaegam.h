@@ -379,6 +379,36 @@ int vg_adam_advance(double* state, double lr, double b1, double b2, void* stream
 int vg_adam_step(void* p, const void* g, void* m, void* v, int64_t n, int32_t is_f64,
                  double b1, double b2, double eps, const double* step_scalars, void* stream);
 
+/* gradient guard (opt-in; an extension, the reference has none): global-norm clipping and a non-finite step skip decided ON THE
+ * DEVICE, inside the (captured) step, from the optimiser's two flat gradient buffers (g32: n32 fp32 elements, g64: n64 fp64
+ * elements; either may be empty: pointer NULL and count 0).
+ * vg_grad_guard = two launches: (1) per-block fp64 partial sums of squares of both buffers into ws (vg_grad_guard_ws_bytes);
+ * every element belongs to a fixed thread of a fixed block and the grid depends on n32 / n64 only, so the partials and (2) their
+ * fixed-order sum are bit-identical from run to run and on every data-parallel rank that holds the same all-reduced buffers: all
+ * ranks take the same decision with no further collective.  No floating-point atomics, no arrival counter.  A sum of squares is
+ * finite exactly when every element is (squares cannot cancel; an fp64 element beyond 1e154 overflows and counts as non-finite).
+ * state = double[VG_GUARD_STATE_LEN], read and written on the device only:
+ *   [0] total_norm   sqrt of the last step's sum of squares (inf / nan as it comes)
+ *   [1] scale        max_norm > 0: c = max_norm / (total_norm + 1e-6), c > 1 ? 1 : c  (torch.nn.utils.clip_grad_norm_; a nan norm
+ *                    gives nan, an inf norm 0, as there); max_norm <= 0 (clipping off): 1
+ *   [2] apply        0 when the norm is non-finite and skip_nonfinite != 0, else 1
+ *   [3] seen         steps the guard has looked at
+ *   [4] skipped      steps with apply = 0
+ *   [5] clipped      finite steps with scale < 1
+ *   [6] norm_sum     sum of total_norm over the finite steps
+ *   [7] norm_max     max of total_norm over the finite steps
+ * [3..7] accumulate until the caller zeroes them.  The gradient buffers are NOT scaled: vg_adam_step_guarded multiplies on load.
+ * vg_adam_advance_guarded = vg_adam_advance, but t and the two scalars move only when guard[2] != 0 (a skipped step must not
+ * advance the bias corrections of the later ones).  vg_adam_step_guarded = vg_adam_step with g * guard[1]; with guard[2] == 0 it
+ * returns without touching p, m, v.  With scale = 1 and apply = 1 both give bit-for-bit what the plain entry points give. */
+#define VG_GUARD_STATE_LEN 8
+int64_t vg_grad_guard_ws_bytes(int64_t n32, int64_t n64);
+int vg_grad_guard(const float* g32, int64_t n32, const double* g64, int64_t n64, double max_norm, int32_t skip_nonfinite,
+                  void* ws, double* state, void* stream);
+int vg_adam_advance_guarded(double* state, double lr, double b1, double b2, const double* guard, void* stream);
+int vg_adam_step_guarded(void* p, const void* g, void* m, void* v, int64_t n, int32_t is_f64,
+                         double b1, double b2, double eps, const double* step_scalars, const double* guard, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

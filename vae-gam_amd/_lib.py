@@ -102,7 +102,12 @@ _PROTOS = {
     'vg_gp_gain_bwd_tiled': (ctypes.c_int, [ctypes.POINTER(GainDesc), vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp]),
     'vg_adam_advance': (ctypes.c_int, [vp, f64, f64, f64, vp]),
     'vg_adam_step': (ctypes.c_int, [vp, vp, vp, vp, i64, i32, f64, f64, f64, vp, vp]),
+    'vg_grad_guard_ws_bytes': (i64, [i64, i64]),
+    'vg_grad_guard': (ctypes.c_int, [vp, i64, vp, i64, f64, i32, vp, vp, vp]),
+    'vg_adam_advance_guarded': (ctypes.c_int, [vp, f64, f64, f64, vp, vp]),
+    'vg_adam_step_guarded': (ctypes.c_int, [vp, vp, vp, vp, i64, i32, f64, f64, f64, vp, vp, vp]),
 }
+GUARD_STATE_LEN = 8            # VG_GUARD_STATE_LEN: [total_norm, scale, apply, seen, skipped, clipped, norm_sum, norm_max]
 EXPORTS = tuple(_PROTOS)
 
 

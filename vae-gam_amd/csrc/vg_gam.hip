@@ -233,6 +233,114 @@ __global__ void adam_advance_k(double* __restrict__ st, double lr, double b1, do
     st[1] = sqrt(1.0 - pow(b2, t));
 }
 
+// ---------------------------------------------------------------------------------- gradient guard
+// Global gradient norm, clip factor and skip decision on the device (state layout: include/vaegam.h).  Sum of squares in fp64 in a
+// FIXED order: element -> thread -> block is a function of (n32, n64) alone (the grid is never sized by the device), each block folds
+// its threads by the same shuffle tree, and one block folds the per-block partials the same way -- the same bits on every run and on
+// every data-parallel rank.  fp32 elements go in quads (one 16-byte load where the buffer is 16-byte aligned; an unaligned buffer walks
+// the same quads with scalar loads, so alignment does not change a bit of the result either).
+constexpr int GG_T = 256, GG_MAXB32 = 256, GG_MAXB64 = 64;
+int gg_blocks32(long long n) { const long long b = (n + GG_T * 16 - 1) / (GG_T * 16); return b > GG_MAXB32 ? GG_MAXB32 : (int)b; }
+int gg_blocks64(long long n) { const long long b = (n + GG_T * 4 - 1) / (GG_T * 4); return b > GG_MAXB64 ? GG_MAXB64 : (int)b; }
+
+__device__ __forceinline__ bool gg_finite(double x) {          // exponent field not all ones (no reliance on how the compiler treats isfinite)
+    union { double d; unsigned long long u; } t; t.d = x;
+    return (t.u & 0x7ff0000000000000ull) != 0x7ff0000000000000ull;
+}
+
+// sum over the block's GG_T threads in a fixed order, valid in thread 0
+__device__ __forceinline__ double gg_block_sum(double a, double* red) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) a += __shfl_down(a, off);
+    if (threadIdx.x % VG_WAVE == 0) red[threadIdx.x / VG_WAVE] = a;
+    __syncthreads();
+    double t = 0;
+    if (threadIdx.x == 0) for (int w = 0; w < GG_T / VG_WAVE; ++w) t += red[w];
+    return t;
+}
+
+// blocks [0, nb32): the fp32 buffer; blocks [nb32, gridDim.x): the fp64 buffer.  part[blockIdx.x] = this block's sum of squares.
+__global__ void __launch_bounds__(GG_T)
+grad_sumsq_k(const float* __restrict__ g32, long long n32, int nb32, const double* __restrict__ g64, long long n64,
+             double* __restrict__ part) {
+    __shared__ double red[GG_T / VG_WAVE];
+    double a = 0;
+    if ((int)blockIdx.x < nb32) {
+        const long long nthr = (long long)nb32 * GG_T, nq = n32 >> 2, me = (long long)blockIdx.x * GG_T + threadIdx.x;
+        const bool vec = ((uintptr_t)g32 & 15) == 0;
+        for (long long q = me; q < nq; q += nthr) {
+            float4 x;
+            if (vec) x = reinterpret_cast<const float4*>(g32)[q];
+            else { x.x = g32[4 * q]; x.y = g32[4 * q + 1]; x.z = g32[4 * q + 2]; x.w = g32[4 * q + 3]; }
+            a += (double)x.x * (double)x.x; a += (double)x.y * (double)x.y; a += (double)x.z * (double)x.z; a += (double)x.w * (double)x.w;
+        }
+        if (me == 0) for (long long i = nq << 2; i < n32; ++i) a += (double)g32[i] * (double)g32[i];      // the up to 3 elements behind the quads
+    } else {
+        const long long nthr = (long long)(gridDim.x - nb32) * GG_T;
+        for (long long i = (long long)(blockIdx.x - nb32) * GG_T + threadIdx.x; i < n64; i += nthr) a += g64[i] * g64[i];
+    }
+    const double t = gg_block_sum(a, red);
+    if (threadIdx.x == 0) part[blockIdx.x] = t;
+}
+
+// one block: fixed-order sum of the partials, then thread 0 derives norm / scale / apply and moves the counters
+__global__ void __launch_bounds__(GG_T)
+grad_guard_final_k(const double* __restrict__ part, int np, double max_norm, int skip_nonfinite, double* __restrict__ st) {
+    __shared__ double red[GG_T / VG_WAVE];
+    double a = 0;
+    for (int k = threadIdx.x; k < np; k += GG_T) a += part[k];
+    const double ss = gg_block_sum(a, red);
+    if (threadIdx.x != 0) return;
+    const bool finite = gg_finite(ss);
+    const double norm = sqrt(ss);
+    double scale = 1.0;
+    if (max_norm > 0) { const double c = max_norm / (norm + 1e-6); scale = c > 1.0 ? 1.0 : c; }      // a nan norm stays nan, as clamp(max=1) leaves it
+    const double apply = (!finite && skip_nonfinite) ? 0.0 : 1.0;
+    st[0] = norm; st[1] = scale; st[2] = apply;
+    st[3] += 1.0;
+    if (apply == 0.0) st[4] += 1.0;
+    if (finite) {
+        if (scale < 1.0) st[5] += 1.0;
+        st[6] += norm;
+        if (norm > st[7]) st[7] = norm;
+    }
+}
+
+// the scaled gradient as a LEAF of the update's arithmetic, as the loaded gradient is in adam_k: left visible, the compiler may contract
+// g * scale into the expressions that use it and pick other fused multiply-adds than adam_k's -- measured on gfx950 as fp64 moments that
+// differ in the last bit at scale = 1, where the guarded update promises adam_k's bits
+#ifdef VG_EMU
+template <typename T> static inline T gg_leaf(T v) { return v; }
+#else
+template <typename T> __device__ __forceinline__ T gg_leaf(T v) { asm volatile("" : "+v"(v)); return v; }
+#endif
+
+// adam_k reading the guard's verdict: the gradient is scaled on load (the buffer keeps the raw gradient), a skipped step writes nothing
+template <typename T>
+__global__ void __launch_bounds__(256)
+adam_guarded_k(T* __restrict__ p, const T* __restrict__ g, T* __restrict__ m, T* __restrict__ v, long long n,
+               double b1, double b2, double eps, const double* __restrict__ sc, const double* __restrict__ guard) {
+    if (guard[2] == 0.0) return;
+    const T step_size = (T)sc[0], bc2_sqrt = (T)sc[1], scale = (T)guard[1];
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+        const T gi = gg_leaf(g[i] * scale);
+        const T mi = m[i] + (gi - m[i]) * (T)(1.0 - b1);
+        const T vi = v[i] * (T)b2 + (T)(1.0 - b2) * gi * gi;
+        m[i] = mi; v[i] = vi;
+        const T denom = sqrt(vi) / bc2_sqrt + (T)eps;
+        p[i] = p[i] - step_size * (mi / denom);
+    }
+}
+
+// adam_advance_k that stands still on a skipped step: t counts the updates that were applied
+__global__ void adam_advance_guarded_k(double* __restrict__ st, double lr, double b1, double b2, const double* __restrict__ guard) {
+    if (threadIdx.x != 0 || blockIdx.x != 0 || guard[2] == 0.0) return;
+    const double t = st[2] + 1.0;
+    st[2] = t;
+    st[0] = lr / (1.0 - pow(b1, t));
+    st[1] = sqrt(1.0 - pow(b2, t));
+}
+
 // ---------------------------------------------------------------------------------- weight packing
 // all conv / transposed-conv weights of the model -> the [ci][tap][co] images the conv kernels read through the scalar
 // path (forward and data-gradient variants), in ONE launch straight from the flat parameter buffer
@@ -355,4 +463,46 @@ extern "C" int vg_adam_step(void* p, const void* g, void* m, void* v, int64_t n,
         vg_launch(adam_k<float>, dim3((unsigned)blocks), dim3(256), 0, s, (float*)p, (const float*)g, (float*)m, (float*)v,
                   (long long)n, b1, b2, eps, step_scalars);
     return vg_check_launch("adam");
+}
+
+extern "C" int64_t vg_grad_guard_ws_bytes(int64_t n32, int64_t n64) {
+    if (n32 < 0 || n64 < 0 || n32 + n64 <= 0) return -1;
+    return (int64_t)(gg_blocks32(n32) + gg_blocks64(n64)) * (int64_t)sizeof(double);
+}
+
+extern "C" int vg_grad_guard(const float* g32, int64_t n32, const double* g64, int64_t n64, double max_norm, int32_t skip_nonfinite,
+                             void* ws, double* state, void* stream) {
+    if (n32 < 0 || n64 < 0 || n32 + n64 <= 0 || (n32 > 0 && !g32) || (n64 > 0 && !g64) || !ws || !state || max_norm != max_norm) {
+        vg_set_error("vg_grad_guard: bad arguments n32=%lld n64=%lld", (long long)n32, (long long)n64); return VG_ERR_ARG;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    const int nb32 = gg_blocks32(n32), nb = nb32 + gg_blocks64(n64);
+    vg_launch(grad_sumsq_k, dim3((unsigned)nb), dim3(GG_T), 0, s, g32, (long long)n32, nb32, g64, (long long)n64, (double*)ws);
+    int rc = vg_check_launch("grad_sumsq");
+    if (rc) return rc;
+    vg_launch(grad_guard_final_k, dim3(1), dim3(GG_T), 0, s, (const double*)ws, nb, max_norm, (int)(skip_nonfinite != 0), state);
+    return vg_check_launch("grad_guard_final");
+}
+
+extern "C" int vg_adam_advance_guarded(double* state, double lr, double b1, double b2, const double* guard, void* stream) {
+    if (!state || !guard || !(lr > 0) || !(b1 >= 0 && b1 < 1) || !(b2 >= 0 && b2 < 1)) {
+        vg_set_error("vg_adam_advance_guarded: bad arguments"); return VG_ERR_ARG;
+    }
+    vg_launch(adam_advance_guarded_k, dim3(1), dim3(64), 0, (hipStream_t)stream, state, lr, b1, b2, guard);
+    return vg_check_launch("adam_advance_guarded");
+}
+
+extern "C" int vg_adam_step_guarded(void* p, const void* g, void* m, void* v, int64_t n, int32_t is_f64,
+                                    double b1, double b2, double eps, const double* step_scalars, const double* guard, void* stream) {
+    if (!p || !g || !m || !v || !step_scalars || !guard || n <= 0) { vg_set_error("vg_adam_step_guarded: bad arguments"); return VG_ERR_ARG; }
+    long long blocks = (n + 255) / 256;
+    if (blocks > 2048) blocks = 2048;
+    hipStream_t s = (hipStream_t)stream;
+    if (is_f64)
+        vg_launch(adam_guarded_k<double>, dim3((unsigned)blocks), dim3(256), 0, s, (double*)p, (const double*)g, (double*)m, (double*)v,
+                  (long long)n, b1, b2, eps, step_scalars, guard);
+    else
+        vg_launch(adam_guarded_k<float>, dim3((unsigned)blocks), dim3(256), 0, s, (float*)p, (const float*)g, (float*)m, (float*)v,
+                  (long long)n, b1, b2, eps, step_scalars, guard);
+    return vg_check_launch("adam_guarded");
 }

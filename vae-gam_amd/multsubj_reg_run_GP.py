@@ -45,6 +45,11 @@ def build_parser():
     parser.add_argument('--gp_jitter', type=float, metavar='N', default=0.0,
                         help='(extension) Ku + jitter*I in the GP posteriors; 0 = the reference\'s plain inverse. Needed for dense inducing grids '
                              '(e.g. --num_inducing_pts 64: 1e-4), where Ku is singular in any precision.')
+    parser.add_argument('--max_grad_norm', type=float, metavar='N', default=None,
+                        help='(extension) Clip the global gradient norm to N inside the step (torch.nn.utils.clip_grad_norm_\'s factor). Default: off.')
+    parser.add_argument('--skip_nonfinite', type=str2bool, nargs='?', const=True, default=False,
+                        help='(extension) Skip a step whose gradient holds an inf / nan (parameters and Adam state untouched) instead of '
+                             'writing it into every parameter; skipped steps are counted and reported per epoch.')
     return parser
 
 
@@ -75,12 +80,15 @@ def main(argv=None):
     model = vae_reg.VAE(num_inducing_pts=args.num_inducing_pts, gp_kl_scale=args.gp_kl_scale,
                         glm_reg_scale=args.glm_reg_scale, glm_maps=args.glm_maps, save_dir=args.save_dir,
                         csv_files=[args.train_csv, args.test_csv], neural_covariates=args.neural_covariates,
-                        data_parallel=dp, dp_gain=os.environ.get('VG_DP_GAIN', 'global'), gp_jitter=args.gp_jitter)
+                        data_parallel=dp, dp_gain=os.environ.get('VG_DP_GAIN', 'global'), gp_jitter=args.gp_jitter,
+                        max_grad_norm=args.max_grad_norm, skip_nonfinite=args.skip_nonfinite)
     if args.from_ckpt:
         assert os.path.exists(args.ckpt_path), 'Oops, looks like ckpt file given does NOT exist!'
         print('=' * 40)
         print('Loading model state from: {}'.format(args.ckpt_path))
         model.load_state(filename=args.ckpt_path)
+        if args.max_grad_norm is not None or args.skip_nonfinite:       # the checkpoint brings its own guard setting (none = off);
+            model.set_grad_guard(args.max_grad_norm, args.skip_nonfinite)   # flags given on this command line take precedence
     if not args.recons_only:
         model.train_loop(loaders_dict, epochs=args.epochs, test_freq=args.test_freq, save_freq=args.save_freq,
                          save_dir=args.save_dir)

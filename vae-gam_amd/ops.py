@@ -1119,6 +1119,45 @@ def adam_step_(p, g, m, v, b1, b2, eps, step_scalars):
              float(eps), _p(_chk(step_scalars, torch.float64)))
 
 
+# --------------------------------------------------------------------------- gradient guard (opt-in; include/vaegam.h)
+GUARD_STATE_LEN = _lib.GUARD_STATE_LEN
+GUARD_NORM, GUARD_SCALE, GUARD_APPLY, GUARD_SEEN, GUARD_SKIPPED, GUARD_CLIPPED, GUARD_NORM_SUM, GUARD_NORM_MAX = range(8)
+
+
+def grad_guard_ws(g32, g64):
+    """Workspace for grad_guard_ over these two flat gradient buffers (either may be None): the per-block partial sums."""
+    ref = g32 if g32 is not None else g64
+    n = _lib.get_lib().size('vg_grad_guard_ws_bytes', 0 if g32 is None else g32.numel(), 0 if g64 is None else g64.numel())
+    return torch.empty(n // 8, dtype=torch.float64, device=ref.device)
+
+
+def grad_guard_(g32, g64, max_norm, skip_nonfinite, ws, state):
+    """Global norm of the two flat gradient buffers -> state = double[8] on the device: total_norm, clip scale, apply flag and the
+    running counters.  max_norm None / <= 0: clipping off (scale 1).  Two launches, nothing comes back to the host."""
+    ref = g32 if g32 is not None else g64
+    if g32 is not None:
+        _chk(g32, torch.float32)
+    if g64 is not None:
+        _chk(g64, torch.float64)
+    assert state.numel() == GUARD_STATE_LEN
+    _call(ref, 'vg_grad_guard', _p(g32), 0 if g32 is None else g32.numel(), _p(g64), 0 if g64 is None else g64.numel(),
+          float(max_norm) if max_norm else 0.0, int(bool(skip_nonfinite)), _p(_chk(ws, torch.float64)), _p(_chk(state, torch.float64)))
+
+
+def adam_advance_guarded_(state, lr, b1, b2, guard):
+    """adam_advance_ that leaves t and the scalars alone when the guard's apply flag is 0."""
+    _call(state, 'vg_adam_advance_guarded', _p(_chk(state, torch.float64)), float(lr), float(b1), float(b2),
+          _p(_chk(guard, torch.float64)))
+
+
+def adam_step_guarded_(p, g, m, v, b1, b2, eps, step_scalars, guard):
+    """adam_step_ on g * scale; touches nothing when the guard's apply flag is 0.  g itself is left unscaled."""
+    assert p.dtype == g.dtype == m.dtype == v.dtype and p.dtype in (torch.float32, torch.float64)
+    assert p.is_contiguous() and g.is_contiguous() and m.is_contiguous() and v.is_contiguous()
+    _call(p, 'vg_adam_step_guarded', _p(p), _p(g), _p(m), _p(v), p.numel(), int(p.dtype == torch.float64), float(b1), float(b2),
+          float(eps), _p(_chk(step_scalars, torch.float64)), _p(_chk(guard, torch.float64)))
+
+
 # --------------------------------------------------------------------------- matrix-core convolution plans (vg_conv_mm)
 USE_MM = int(_os.environ.get('VG_CONV_MM', '1'))            # 0: off; 1: where it measured faster (mm_wins); 2: wherever a plan exists
 _MM_LDS_BUDGET = 150 * 1024

@@ -97,7 +97,7 @@ class VAE(nn.Module):
     def __init__(self, nf=8, save_dir='', lr=1e-3, num_covariates=8, num_latents=32, device_name="auto",
                  num_inducing_pts=6, gp_kl_scale=10.0, glm_maps='', glm_reg_scale=1.0, csv_files='',
                  neural_covariates=True, *, img_shape=IMG_SHAPE, xu_ranges=None, tensorboard=False,
-                 data_parallel=None, gp_jitter=0.0, dp_gain='global'):
+                 data_parallel=None, gp_jitter=0.0, dp_gain='global', max_grad_norm=None, skip_nonfinite=False):
         """Arguments up to `neural_covariates` are the reference's (vae_reg_GP.py:36-37).
         Keyword-only extensions: `img_shape` (41x49x35 or 82x98x70), `xu_ranges` (inducing-point
         ranges given directly instead of read from `csv_files`), `tensorboard` (off by default),
@@ -118,6 +118,12 @@ class VAE(nn.Module):
         GLOBAL batch index across the slices (ops.HrfAcrossRanks).  A different stochastic estimate of the loss than the 1-rank
         global-batch step (same expectation for the non-HRF covariates; for an HRF covariate the 14 volumes behind a slice boundary
         lose the cross-slice covariance terms of their convolved gain); kept as an option: its cost does not grow with the ranks.
+        `max_grad_norm` / `skip_nonfinite` (both off by default; also VAE.set_grad_guard on a built model): the gradient guard.  Inside
+        the step, on the device, after the data-parallel all-reduce: the global L2 norm of all gradients; `max_grad_norm` clips to it
+        with torch.nn.utils.clip_grad_norm_'s factor min(1, max_norm / (norm + 1e-6)); `skip_nonfinite` turns a step whose gradient
+        holds an inf / nan into a no-op (parameters, Adam moments and Adam's step count untouched) instead of writing it into every
+        parameter.  No host read-back, so it is captured into the hipGraph with the rest of the step.  The clip factor is applied as
+        the update reads the gradient: `p.grad` stays the raw gradient.  Counters: optimizer.guard_stats().
         `glm_maps` may be a CSV path
         (reference) or an array of shape (V, C+1) whose column 0 is the CSV index column."""
         super(VAE, self).__init__()
@@ -178,7 +184,8 @@ class VAE(nn.Module):
         named = list(self.named_parameters())
         head_groups = [['fc31.weight', 'fc32.weight', 'fc33.weight'], ['fc31.bias', 'fc32.bias', 'fc33.bias'],
                        ['fc41.weight', 'fc42.weight', 'fc43.weight'], ['fc41.bias', 'fc42.bias', 'fc43.bias']]
-        self.optimizer = FusedAdam(named, lr=self.lr, contiguous_groups=head_groups)
+        self.optimizer = FusedAdam(named, lr=self.lr, contiguous_groups=head_groups, max_grad_norm=max_grad_norm,
+                                   skip_nonfinite=skip_nonfinite)
         self._heads = None
         hv = [self.optimizer.group_views(g_) for g_ in head_groups]
         if all(v is not None for v in hv):
@@ -211,6 +218,23 @@ class VAE(nn.Module):
         self.recon_sums = None         # per-subject map sums left by reconstruct() for build_model_recons.mk_avg_maps
         self._graphs = {}
         self.last_gp_kl = None
+
+    # ------------------------------------------------------------------ gradient guard
+    @property
+    def max_grad_norm(self):
+        return self.optimizer.max_grad_norm
+
+    @property
+    def skip_nonfinite(self):
+        return self.optimizer.skip_nonfinite
+
+    def set_grad_guard(self, max_grad_norm=None, skip_nonfinite=False):
+        """Change the gradient guard of a built model (see __init__); both off = the plain step.  Captured steps hold the launches of
+        the previous setting, so the graphs are dropped and re-captured on the next train_step."""
+        if self.device.type == 'cuda':
+            torch.cuda.current_stream(self.device).synchronize()     # queued replays still read the state block about to be reset
+        self.optimizer.set_guard(max_grad_norm, skip_nonfinite)
+        self._graphs.clear()
 
     # ------------------------------------------------------------------ construction helpers
     _GAIN_PREFIXES = ('sa_', 'logstd_', 'qu_m_', 'qu_S_', 'logkvar_', 'logls_')
@@ -610,7 +634,7 @@ class VAE(nn.Module):
         # parameters / optimiser state are restored after the warm-up + capture passes, so that enabling the
         # graph does not change the training trajectory (the capture itself executes nothing)
         snap = [(g, g['p'].clone(), g['m'].clone(), g['v'].clone()) for g in self.optimizer.groups.values()]
-        step0 = self.optimizer.step_count
+        counters = self.optimizer.counters_snapshot()
         torch.cuda.current_stream(x.device).synchronize()       # everything queued so far has used the device-side count
         rng = torch.cuda.get_rng_state(x.device)
         try:
@@ -636,7 +660,7 @@ class VAE(nn.Module):
                     raise
             for g, p0, m0, v0 in snap:
                 g['p'].copy_(p0); g['m'].copy_(m0); g['v'].copy_(v0)
-            self.optimizer.set_step_count(step0)
+            self.optimizer.counters_restore(counters)
             torch.cuda.set_rng_state(rng, x.device)
             st['graph'] = graph
             self._graphs[key] = st
@@ -646,7 +670,7 @@ class VAE(nn.Module):
             torch.cuda.synchronize()
             for g, p0, m0, v0 in snap:
                 g['p'].copy_(p0); g['m'].copy_(m0); g['v'].copy_(v0)
-            self.optimizer.set_step_count(step0)
+            self.optimizer.counters_restore(counters)
             torch.cuda.set_rng_state(rng, x.device)
         if self.dp is not None:
             # every rank must make the same choice (a graph replays its collectives, an eager rank issues them one by one)
@@ -661,7 +685,13 @@ class VAE(nn.Module):
         total = torch.zeros((), dtype=torch.float64, device=self.device)
         for batch_idx, sample in enumerate(train_loader):
             ids, covariates, x = self._batch_to_device(sample)
-            total += self.train_step(ids, covariates, x).sum().double()
+            step_loss = self.train_step(ids, covariates, x).sum().double()
+            if self.optimizer.skip_nonfinite:
+                # a skipped step's loss (non-finite, and no update was made from it) stays out of the epoch mean; the flag is read
+                # on the device, behind the step that wrote it
+                applied = self.optimizer.guard_state[ops.GUARD_APPLY] != 0
+                step_loss = torch.where(applied, step_loss, torch.zeros_like(step_loss))
+            total += step_loss
         train_loss = float(total.item()) / len(train_loader.dataset)     # one sync per epoch (the reference syncs per batch, :426)
         print('Epoch: {} Average loss: {:.4f}'.format(self.epoch, train_loss))
         self.epoch += 1
@@ -692,6 +722,7 @@ class VAE(nn.Module):
             self.loss['train'][epoch] = loss
             self.writer.add_scalar("Loss/Train", loss, self.epoch)
             self._log_gain_scalars()
+            self._log_grad_guard()
             self.writer.flush()
             if (test_freq is not None) and (epoch % test_freq == 0):
                 loss = self.test_epoch(loaders['test'])
@@ -702,6 +733,18 @@ class VAE(nn.Module):
                 file_path = os.path.join(save_dir, filename)
                 self.save_state(file_path)                      # data parallel: replicas are identical, rank 0 writes
         self.writer.close()
+
+    def _log_grad_guard(self):
+        """Once per epoch: the guard's counters of this epoch (they restart here) to the writer, and one line if steps were skipped."""
+        st = self.optimizer.guard_stats(reset=True)
+        if st is None:
+            return
+        if st['skipped'] and (self.dp is None or self.dp.rank == 0):
+            print('Gradient guard: skipped {} of {} steps (non-finite gradient)'.format(st['skipped'], st['seen']))
+        self.writer.add_scalar('GradGuard/norm_mean', st['norm_mean'], self.epoch)
+        self.writer.add_scalar('GradGuard/norm_max', st['norm_max'], self.epoch)
+        self.writer.add_scalar('GradGuard/skipped', st['skipped'], self.epoch)
+        self.writer.add_scalar('GradGuard/clipped', st['clipped'], self.epoch)
 
     def _log_gain_scalars(self):
         """Per-epoch gain / GP hyper-parameters (what utils.log_beta / log_qkappa_plots trace per forward in the reference)."""
@@ -736,6 +779,10 @@ class VAE(nn.Module):
         state['inducing_pts'] = self.inducing_pts
         if self.gp_jitter:                                # extra key, only when the extension is in use (the reference's loader ignores it):
             state['gp_jitter'] = self.gp_jitter          # the posterior that was trained is the one a resumed run / the export evaluates
+        if self.max_grad_norm is not None:                # the gradient guard's settings, likewise only when in use
+            state['max_grad_norm'] = self.max_grad_norm
+        if self.skip_nonfinite:
+            state['skip_nonfinite'] = True
         gp_out = {}
         for cov, d in self.gp_params.items():
             gp_out[cov] = {k: (torch.nn.Parameter(v.detach().clone()) if isinstance(v, torch.nn.Parameter) else v.clone())
@@ -773,6 +820,9 @@ class VAE(nn.Module):
         self._gain_const_cache.clear()
         self._graphs.clear()
         self._glm_f32 = None
+        # the guard the checkpointed run trained under; a checkpoint without the keys (the reference's, or a run without the guard)
+        # loads with it off
+        self.set_grad_guard(checkpoint.get('max_grad_norm'), bool(checkpoint.get('skip_nonfinite', False)))
 
     # ------------------------------------------------------------------ post-hoc (reconstruction export lives in build_model_recons)
     def reconstruct(self, loader, ref_niis, save_dirs, write_volumes=True, noise=None):
