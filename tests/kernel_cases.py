@@ -344,6 +344,244 @@ def run_conv_mm_plan_case(dev, kind, force, seed=0):
     np.testing.assert_allclose(got.cpu().numpy(), want.numpy(), rtol=2e-4, atol=2e-4, err_msg='%s %r' % (kind, force))
 
 
+_K3 = (3, 3, 3)
+# the layers whose launches vg_conv_mm carries in the three schema.net_geometry networks (41x49x35, 82x98x70, 21x21x21)
+MM_SPECS = {
+    'conv2': ConvSpec('conv', 8, 8, _K3, 2),
+    'conv3': ConvSpec('conv', 8, 16, _K3, 1),
+    'conv4': ConvSpec('conv', 16, 16, _K3, 2),
+    'conv5': ConvSpec('conv', 16, 16, _K3, 1),
+    'convt1': ConvSpec('convt', 16, 16, _K3, 1),
+    'convt2p': ConvSpec('convt', 16, 16, _K3, 2, (1, 0, 1), (1, 0, 1)),      # the padded convt2 of the 41x49x35 network
+    'convt2': ConvSpec('convt', 16, 16, _K3, 2),                             # the plain one of the 82x98x70 network
+    'convt3': ConvSpec('convt', 16, 8, _K3, 1),
+    'convt4': ConvSpec('convt', 8, 8, (5, 3, 3), 2),
+    'convt4hr': ConvSpec('convt', 8, 8, (4, 4, 4), 2),                       # 82x98x70
+    'convt4toy': ConvSpec('convt', 8, 8, _K3, 2),                            # 21x21x21
+}
+
+
+def mm_instance(plan, masked):
+    """(W, NQ, TPC, ks, DB, MASKED) of the conv_mm_k instance vg_conv_mm launches for this plan -- a restatement of its dispatch, for
+    the record a case prints (ks 0 = the generic instance that reads the step counts from the descriptor)."""
+    ks = list(plan.ks)
+    if plan.nq == 1:
+        static = ks[0] in (7, 9, 12) or (ks[0] == 19 and plan.tpc <= 3)
+    else:
+        static = ks in ([3, 2, 2, 1], [2, 1, 1, 1], [2, 2, 2, 2])
+    return (plan.waves, plan.nq, plan.tpc, tuple(ks) if static else 0, plan.dbuf, int(bool(masked)))
+
+
+def run_conv_mm_case(dev, spec, direction, isz, force, groups=2, per_group=3, stats=False, seed=0, tpc=None, loop=False):
+    """One vg_conv_mm launch with a PINNED tile (waves, PD planes, PHB rows, channels per chunk, double buffering) against float64
+    F.conv3d / F.conv_transpose3d on the CPU.  `isz` is the LAYER's input size: 'fwd' reads it (prologue = ReLU + per-(group, channel)
+    affine, bias added; with `stats` also the partial sums of the next batch norm), 'bwd' reads dy of the layer's output size and
+    writes the data gradient, masked by the producer's pre-activation.  `loop`: the case is sized so that a block of the persistent
+    grid must visit several samples (N * blocks per sample > 2048 = 256 CUs x at most 8 resident blocks).
+
+    Tolerance: tol = max(4 * d32, eps32 * sqrt(K) * max|want|) with d32 = the distance of torch's own fp32 CPU convolution to the
+    float64 result on the same inputs and K = CI * taps the contraction length (the random-walk rounding floor of an fp32 sum of K
+    terms: guards against a lucky tiny d32).  The fp32 matrix cores are exact fp32 FMAs in another summation order, so the kernel's
+    error is of d32's size: 0.6x to 2.4x over the listed cases on the host build; a path that lost precision would sit at 100x or more.
+
+    Statistics: mean and rstd of relu(y) per (group, channel) from the kernel's partials against float64 statistics of the float64
+    reference.  Bound: every element of y is within tol and relu is 1-Lipschitz; the partial sums are fp32 chains of non-negative
+    terms, at most m = tpc * nq * per_group elements per lane and run plus 6 shuffle stages, so they are relatively exact to
+    m * eps32 (sums) / (m + 1) * eps32 (squares, one fma rounding more): |d mean| <= tol + m eps32 mean,
+    |d E[h^2]| <= 2 max|h| tol + (m + 1) eps32 E[h^2], |d var| <= |d E[h^2]| + 2 mean |d mean| + |d mean|^2, and rstd moves by what
+    var +- d var moves it; both are stored in fp32 (one more eps32).
+
+    Returns the record of the case: plan, instance, err, d32, tol."""
+    g = torch.Generator().manual_seed(seed)
+    N = groups * per_group
+    isz = tuple(isz)
+    osz = spec.out_size(isz)
+    conv = spec.kind == 'conv'
+    wshape = ((spec.co, spec.ci) if conv else (spec.ci, spec.co)) + tuple(spec.k)
+    w = 0.2 * torch.randn(wshape, generator=g)
+    taps = spec.k[0] * spec.k[1] * spec.k[2]
+    eps32 = float(np.finfo(np.float32).eps)
+
+    def layer(h, wt, bias):
+        if conv:
+            return F.conv3d(h, wt, bias, spec.stride)
+        return F.conv_transpose3d(h, wt, bias, spec.stride, spec.pad, spec.outpad)
+
+    if direction == 'fwd':
+        plan = ops.mm_plan(spec, 'fwd', isz, None, force=force)
+    else:
+        plan = ops.mm_plan(spec, 'bwd', osz, isz, force=force)
+    assert plan is not None, (spec, direction, isz, force)
+    assert (plan.waves, plan.PD, plan.PHB, plan.cc, plan.dbuf) == tuple(force)
+    if tpc is not None:
+        assert plan.tpc == tpc, (plan.tpc, tpc)
+    nslab = (plan.PH + plan.PHB - 1) // plan.PHB
+    bps = ((plan.PDT + plan.PD - 1) // plan.PD) * nslab
+    if loop:
+        assert N * bps > 2048, (N, bps)
+
+    if direction == 'fwd':
+        x = torch.randn((N, spec.ci) + isz, generator=g)
+        b = 0.1 * torch.randn(spec.co, generator=g)
+        sc = 1 + 0.3 * torch.randn(groups * spec.ci, generator=g); sh = 0.2 * torch.randn(groups * spec.ci, generator=g)
+
+        def pro(t, dt):
+            a = sc.to(dt).view(groups, 1, spec.ci, 1, 1, 1).expand(groups, per_group, spec.ci, 1, 1, 1).reshape(N, spec.ci, 1, 1, 1)
+            c = sh.to(dt).view(groups, 1, spec.ci, 1, 1, 1).expand(groups, per_group, spec.ci, 1, 1, 1).reshape(N, spec.ci, 1, 1, 1)
+            return torch.relu(t.to(dt)) * a + c
+        want = layer(pro(x, torch.float64), w.double(), b.double())
+        own32 = layer(pro(x, torch.float32), w, b)
+        K = spec.ci * taps
+        nb = per_group if stats else None
+        got = ops.conv_mm(x.to(dev), plan, plan.gather(w.to(dev)), b.to(dev), True, sc.to(dev), sh.to(dev), per_group, None, nb)
+        if stats:
+            got, part = got
+    else:
+        assert not stats
+        dy = torch.randn((N, spec.co) + osz, generator=g)
+        xm = torch.randn((N, spec.ci) + isz, generator=g)              # the producer's pre-activation: ReLU mask of the data gradient
+
+        def dgrad(dt):
+            x0 = torch.zeros((N, spec.ci) + isz, dtype=dt, requires_grad=True)
+            (gx,) = torch.autograd.grad(layer(x0, w.to(dt), None), x0, dy.to(dt))
+            return gx * (xm > 0)
+        want = dgrad(torch.float64)
+        own32 = dgrad(torch.float32)
+        K = spec.co * taps
+        got = ops.conv_mm(dy.to(dev), plan, plan.gather(w.to(dev)), None, False, None, None, 1, xm.to(dev))
+    assert tuple(got.shape) == tuple(want.shape), (got.shape, want.shape)
+    d32 = float((own32.double() - want).abs().max())
+    wmax = float(want.abs().max())
+    tol = max(4 * d32, eps32 * K ** 0.5 * wmax)
+    err = float((got.cpu().double() - want).abs().max())
+    rec = dict(spec=spec, direction=direction, isz=isz, force=tuple(force), N=N, bps=bps, nslab=nslab, mode=plan.mode, stride=spec.stride,
+               cc=plan.cc, CI=plan.CI, instance=mm_instance(plan, direction == 'bwd'), err=err, d32=d32, tol=tol, stats=stats)
+    print('conv_mm %s %s isz %r force %r N %d bps %d nslab %d instance (W, NQ, TPC, ks, DB, MASKED) %r: err %.3g d32 %.3g err/d32 %.2f tol %.3g'
+          % (spec.kind + 'x'.join(map(str, spec.k)) + '_%d>%d_s%d' % (spec.ci, spec.co, spec.stride), direction, isz, tuple(force), N, bps,
+             nslab, rec['instance'], err, d32, err / max(d32, 1e-30), tol))
+    assert err <= tol, 'conv_mm %s %r %r: max error %.3g > tol %.3g (d32 %.3g)' % (direction, isz, tuple(force), err, tol, d32)
+    if stats:
+        gamma = torch.ones(spec.co, device=dev); beta = torch.zeros(spec.co, device=dev)
+        _, _, mean, rstd = ops.bn_stats(got, gamma, beta, True, per_group, pre=part)
+        h = torch.relu(want).reshape(groups, per_group, spec.co, -1)
+        mean_w = h.mean((1, 3)).reshape(-1); e2_w = (h * h).mean((1, 3)).reshape(-1)
+        var_w = e2_w - mean_w * mean_w
+        rstd_w = (var_w + ops.BN_EPS).rsqrt()
+        m = plan.tpc * plan.nq * per_group + 6
+        hmax = float(h.max())
+        dmean = tol + m * eps32 * mean_w
+        de2 = 2 * hmax * tol + (m + 1) * eps32 * e2_w
+        dvar = de2 + 2 * mean_w * dmean + dmean * dmean
+        assert float((var_w + ops.BN_EPS - dvar).min()) > 0
+        drstd = torch.maximum((var_w + ops.BN_EPS - dvar).rsqrt() - rstd_w, rstd_w - (var_w + ops.BN_EPS + dvar).rsqrt())
+        em = (mean.cpu().double() - mean_w).abs(); er = (rstd.cpu().double() - rstd_w).abs()
+        bm = dmean + eps32 * mean_w.abs(); br = drstd + eps32 * rstd_w
+        print('  statistics: mean err / bound %.3g, rstd err / bound %.3g' % (float((em / bm).max()), float((er / br).max())))
+        assert bool((em <= bm).all()), 'mean of relu(y): worst error / bound %.3g' % float((em / bm).max())
+        assert bool((er <= br).all()), 'rstd of relu(y): worst error / bound %.3g' % float((er / br).max())
+    return rec
+
+
+# (id, spec, direction, layer input size, force = (waves, PD, PHB, cc, dbuf), tpc the plan selects, statistics)
+# N = 6 (2 groups of 3); every size <= 11x13x9.  s = row slabs (nslab >= 2), w = whole planes.
+CONV_MM_CASES = [
+    # conv2 bwd: 4 parity classes ks [2,1,1,1], masked
+    ('conv2_bwd-s', 'conv2', 'bwd', (11, 13, 9), (8, 2, 3, 8, 0), 4, False),
+    ('conv2_bwd-s-w4-db', 'conv2', 'bwd', (11, 13, 9), (4, 1, 2, 8, 1), 4, False),
+    ('conv2_bwd-w-db', 'conv2', 'bwd', (11, 13, 9), (8, 3, 7, 8, 1), 4, False),
+    # conv2 fwd (VG_CONV_MM=2): stride-2 correlation, ks 12, one channel per chunk
+    ('conv2_fwd-s-cc1', 'conv2', 'fwd', (11, 13, 9), (8, 2, 3, 1, 0), 3, False),
+    ('conv2_fwd-w-cc1-db', 'conv2', 'fwd', (11, 13, 9), (4, 5, 6, 1, 1), 3, False),
+    # conv3 fwd (ks 7) / bwd (ks 9): every tiles-per-wave instance
+    ('conv3_fwd-s-cc4', 'conv3', 'fwd', (7, 11, 8), (8, 1, 3, 4, 0), 3, False),
+    ('conv3_fwd-w-db-tpc4', 'conv3', 'fwd', (11, 13, 9), (8, 5, 11, 8, 1), 4, False),
+    ('conv3_fwd-w-cc2-tpc5', 'conv3', 'fwd', (11, 13, 9), (8, 7, 11, 2, 0), 5, False),
+    ('conv3_fwd-s-w4-db-tpc6', 'conv3', 'fwd', (11, 13, 9), (4, 8, 6, 4, 1), 6, False),
+    ('conv3_fwd-w-w4-tpc8', 'conv3', 'fwd', (11, 13, 9), (4, 5, 11, 8, 0), 8, False),
+    ('conv3_bwd-s-db', 'conv3', 'bwd', (7, 11, 8), (8, 2, 4, 4, 1), 3, False),
+    ('conv3_bwd-w-w4-tpc4', 'conv3', 'bwd', (9, 11, 8), (4, 5, 11, 16, 0), 4, False),
+    ('conv3_bwd-w-w4-db-tpc5', 'conv3', 'bwd', (9, 11, 8), (4, 6, 11, 8, 1), 5, False),
+    ('conv3_bwd-w-w4-cc4-tpc6', 'conv3', 'bwd', (9, 11, 8), (4, 8, 11, 4, 0), 6, False),
+    ('convt3_fwd-w-w4-db-tpc8', 'convt3', 'fwd', (7, 11, 7), (4, 6, 13, 8, 1), 8, False),
+    # conv4 fwd: stride-2 correlation, ks 7
+    ('conv4_fwd-s-cc2', 'conv4', 'fwd', (9, 13, 8), (8, 1, 3, 2, 0), 3, False),
+    ('conv4_fwd-s-w4-db', 'conv4', 'fwd', (9, 13, 8), (4, 2, 2, 4, 1), 3, False),
+    ('conv4_fwd-w', 'conv4', 'fwd', (9, 13, 8), (8, 2, 6, 16, 0), 3, False),
+    # conv5 / convt1: the 16 -> 16 stride-1 layers
+    ('conv5_fwd-s-db', 'conv5', 'fwd', (6, 8, 6), (8, 2, 3, 8, 1), 3, False),
+    ('conv5_fwd-w-w4', 'conv5', 'fwd', (6, 8, 6), (4, 4, 6, 16, 0), 3, False),
+    ('conv5_bwd-s-w4', 'conv5', 'bwd', (6, 8, 6), (4, 3, 4, 16, 0), 3, False),
+    ('conv5_bwd-w-db', 'conv5', 'bwd', (6, 8, 6), (8, 3, 8, 8, 1), 3, False),
+    ('convt1_fwd-s', 'convt1', 'fwd', (4, 6, 5), (8, 3, 4, 8, 0), 3, False),
+    ('convt1_fwd-w-db', 'convt1', 'fwd', (4, 6, 5), (8, 3, 8, 16, 1), 3, False),
+    ('convt1_bwd-s-db', 'convt1', 'bwd', (4, 6, 5), (8, 2, 2, 16, 1), 3, False),
+    ('convt1_bwd-w-cc4', 'convt1', 'bwd', (4, 6, 5), (8, 4, 6, 4, 0), 3, False),
+    # convt2 bwd: stride-2 correlation, padded (41x49x35) and plain (82x98x70)
+    ('convt2p_bwd-s-cc2', 'convt2p', 'bwd', (5, 6, 4), (8, 1, 3, 2, 0), 3, False),
+    ('convt2p_bwd-w-db', 'convt2p', 'bwd', (5, 6, 4), (8, 3, 6, 16, 1), 3, False),
+    ('convt2_bwd-s-db', 'convt2', 'bwd', (5, 6, 4), (8, 2, 2, 8, 1), 3, False),
+    ('convt2_bwd-w-w4', 'convt2', 'bwd', (5, 6, 4), (4, 2, 6, 4, 0), 3, False),
+    # convt4 bwd (VG_CONV_MM=2): stride-2 correlation, ks 19, one channel per chunk
+    ('convt4_bwd-s-cc1', 'convt4', 'bwd', (4, 5, 4), (8, 2, 2, 1, 0), 3, False),
+    ('convt4_bwd-w-cc1-db', 'convt4', 'bwd', (4, 5, 4), (8, 4, 5, 1, 1), 3, False),
+    # 4x4x4 convt4 bwd (VG_CONV_MM=2): ks 24, the generic instance
+    ('convt4hr_bwd-s-cc1', 'convt4hr', 'bwd', (4, 5, 3), (8, 2, 3, 1, 0), 3, False),
+    ('convt4hr_bwd-w-w4-cc1-db', 'convt4hr', 'bwd', (4, 5, 3), (4, 2, 5, 1, 1), 3, False),
+    # stride-2 transposed convs forward, statistics of the next batch norm: 4x4x4 (ks [2,2,2,2]) and 3x3x3 (ks [2,1,1,1])
+    ('convt4hr_fwd-s-stats', 'convt4hr', 'fwd', (4, 7, 5), (8, 2, 3, 8, 0), 4, True),
+    ('convt4hr_fwd-s-w4-db-stats', 'convt4hr', 'fwd', (4, 7, 5), (4, 1, 4, 8, 1), 4, True),
+    ('convt4hr_fwd-w-db-stats', 'convt4hr', 'fwd', (4, 7, 5), (8, 2, 8, 8, 1), 4, True),
+    ('convt4toy_fwd-s-stats', 'convt4toy', 'fwd', (4, 7, 5), (8, 2, 4, 8, 0), 4, True),
+    ('convt4toy_fwd-w-w4-db-stats', 'convt4toy', 'fwd', (4, 7, 5), (4, 2, 8, 8, 1), 4, True),
+]
+
+# The persistent sample loop: N * blocks per sample > 2048, so that some block visits several samples whatever the occupancy query
+# returns (nsplit <= 256 * blocks_per_cu / bps, blocks_per_cu <= 8).  per_group 8 / 13 / 7 against strides nsplit = 12, 25, 51, 102:
+# a block's visits cross groups; 2 groups of 103 samples: they also stay inside a group at every possible stride (< 103).
+# (id, spec, direction, layer input size, force, tpc, statistics, groups, per_group)
+CONV_MM_LOOP_CASES = [
+    ('convt4_fwd-stats-13x8', 'convt4', 'fwd', (3, 7, 4), (4, 1, 2, 8, 0), 4, True, 13, 8),
+    ('convt4_fwd-db-stats-8x13', 'convt4', 'fwd', (3, 7, 4), (4, 1, 2, 8, 1), 4, True, 8, 13),
+    ('convt4_fwd-stats-2x103', 'convt4', 'fwd', (3, 7, 1), (4, 1, 2, 8, 0), 4, True, 2, 103),
+    ('convt3_fwd-cc8-11x7', 'convt3', 'fwd', (5, 6, 2), (4, 1, 2, 8, 0), 3, False, 11, 7),
+    ('convt3_bwd-db-masked-11x7', 'convt3', 'bwd', (7, 8, 4), (4, 1, 2, 4, 1), 3, False, 11, 7),
+]
+
+# On the host build a looping case costs what its N * bps * chunks units cost, whatever its shape: these two measured 24 s each
+# (the others 8 to 11 s), above the 20 s a host case may take, so they run on the GPU only (milliseconds there).
+CONV_MM_LOOP_GPU_ONLY = ('convt4_fwd-stats-2x103', 'convt3_fwd-cc8-11x7')
+
+
+def run_conv_mm_listed(dev, case, seed=0):
+    cid, sname, direction, isz, force, tpc, stats = case[:7]
+    groups, per_group = case[7:9] if len(case) > 7 else (2, 3)
+    return run_conv_mm_case(dev, MM_SPECS[sname], direction, isz, force, groups, per_group, stats, seed, tpc=tpc, loop=len(case) > 7)
+
+
+def conv_mm_coverage(dev=None):
+    """What the union of CONV_MM_CASES and CONV_MM_LOOP_CASES pins, from the plans alone (no launch): the sets the issue asks for."""
+    cov = dict(kinds=set(), slab_modes=set(), cc_lt_ci=0, dbuf=set(), waves=set(), masked=set(), tpc=set(), loops=0, loops_stats=0)
+    for case in CONV_MM_CASES + CONV_MM_LOOP_CASES:
+        cid, sname, direction, isz, force, tpc, stats = case[:7]
+        spec = MM_SPECS[sname]
+        plan = ops.mm_plan(spec, 'fwd', isz, None, force=force) if direction == 'fwd' else ops.mm_plan(spec, 'bwd', spec.out_size(isz), isz, force=force)
+        assert plan is not None, cid
+        nslab = (plan.PH + plan.PHB - 1) // plan.PHB
+        bps = ((plan.PDT + plan.PD - 1) // plan.PD) * nslab
+        cov['kinds'].add((sname, direction, 'slab' if nslab > 1 else 'whole'))
+        if nslab > 1:
+            cov['slab_modes'].add('class4' if plan.nq == 4 else 'corr_s%d' % plan.sdi)
+        cov['cc_lt_ci'] += plan.cc < plan.CI
+        cov['dbuf'].add(plan.dbuf); cov['waves'].add(plan.waves); cov['masked'].add(direction == 'bwd')
+        if plan.nq == 1 and plan.ks[0] in (7, 9):
+            cov['tpc'].add((plan.ks[0], plan.tpc))
+        if len(case) > 7:
+            N = case[7] * case[8]
+            assert N * bps > 2048, cid
+            cov['loops'] += 1; cov['loops_stats'] += bool(stats)
+    return cov
+
+
 def run_adam_case(dev, dtype, n=5000, steps=3, seed=0):
     g = torch.Generator().manual_seed(seed)
     p0 = torch.randn(n, generator=g, dtype=dtype)

@@ -8,7 +8,7 @@ import pytest
 import torch
 
 import vae_gam_amd  # noqa: F401
-from vae_gam_amd import _lib
+from vae_gam_amd import _lib, ops
 import kernel_cases as K
 
 EMU_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'emu')
@@ -103,3 +103,49 @@ def test_gain_block_matches_float64_oracle(B, n, jitter):
 ])
 def test_conv_mm_pinned_tiles(kind, force):
     K.run_conv_mm_plan_case('cpu', kind, force)
+
+
+@pytest.mark.parametrize('case', K.CONV_MM_CASES, ids=[c[0] for c in K.CONV_MM_CASES])
+def test_conv_mm_launch_kinds(case):
+    """every launch kind vg_conv_mm carries in the networks, at a pinned row-slab tile and a pinned whole-plane tile, against float64"""
+    K.run_conv_mm_listed('cpu', case)
+
+
+_HOST_LOOP_CASES = [c for c in K.CONV_MM_LOOP_CASES if c[0] not in K.CONV_MM_LOOP_GPU_ONLY]      # the reason stands next to that list
+
+
+@pytest.mark.parametrize('case', _HOST_LOOP_CASES, ids=[c[0] for c in _HOST_LOOP_CASES])
+def test_conv_mm_sample_loop(case):
+    """blocks of the persistent grid visit several samples: statistics flushed per group run, the prologue affine changing group
+    between units, buffer parity / wait order / mask prefetch repeating"""
+    K.run_conv_mm_listed('cpu', case, seed=1)
+
+
+def test_conv_mm_case_matrix_coverage():
+    cov = K.conv_mm_coverage()
+    kinds = [('conv2', 'bwd'), ('conv2', 'fwd'), ('conv3', 'fwd'), ('conv3', 'bwd'), ('conv4', 'fwd'), ('conv5', 'fwd'), ('conv5', 'bwd'),
+             ('convt1', 'fwd'), ('convt1', 'bwd'), ('convt2p', 'bwd'), ('convt2', 'bwd'), ('convt4', 'bwd'), ('convt4hr', 'fwd'),
+             ('convt4hr', 'bwd'), ('convt4toy', 'fwd')]
+    for s, d in kinds:
+        assert (s, d, 'slab') in cov['kinds'] and (s, d, 'whole') in cov['kinds'], (s, d)
+    assert cov['slab_modes'] == {'corr_s1', 'corr_s2', 'class4'}
+    assert cov['cc_lt_ci'] > 0 and cov['dbuf'] == {0, 1} and cov['waves'] == {4, 8} and cov['masked'] == {False, True}
+    assert cov['tpc'] == {(ks, t) for ks in (7, 9) for t in (3, 4, 5, 6, 8)}
+    assert cov['loops'] >= 4 and cov['loops_stats'] >= 2
+
+
+def _layer_args(name, spec):
+    """the arguments of test_layer_bn_relu / test_layer_wide_rows for this layer"""
+    groups = 2 if spec.kind == 'convt' else 1
+    if name in [l[0] for l in K.LAYERS]:
+        return dict(with_bn=True, relu_in=(name != 'conv1'), groups=groups)
+    return dict(with_bn=name.startswith(('conv1', 'conv3', 'convt3', 'convt5')), relu_in=not name.startswith('conv1'), groups=groups, seed=11)
+
+
+@pytest.mark.parametrize('use_mm', [0, 2], ids=['register_tiled', 'matrix_cores'])
+@pytest.mark.parametrize('name,spec,isz', K.LAYERS + K.WIDE_LAYERS, ids=[l[0] for l in K.LAYERS + K.WIDE_LAYERS])
+def test_layer_both_engines(name, spec, isz, use_mm, monkeypatch):
+    """the shrunk layers with the engine choice forced: 0 = the register-tiled kernels everywhere (what the large multi-channel
+    launches run in production), 2 = vg_conv_mm wherever a plan exists (also the plans mm_wins declines)"""
+    monkeypatch.setattr(ops, 'USE_MM', use_mm)
+    K.run_layer_case('cpu', name, spec, isz, **_layer_args(name, spec))
