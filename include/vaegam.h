@@ -99,7 +99,14 @@ int vg_gather_f32(const float* src, const int32_t* idx, float* dst, int64_t n, v
  * b: [N][CB][PD][PH][PW], a: [N][CA][AD][AH][AW] (zero outside).  For a Conv3d layer b = dy,
  * a = layer input (prologue on a); for a ConvTranspose3d layer b = layer input (prologue on b),
  * a = dy.  dw comes out in the layer's own weight layout.  Replaces autograd's conv weight
- * gradients.  `ws` is caller workspace of vg_wgrad3d_ws_bytes() bytes. */
+ * gradients.  `ws` is caller workspace of vg_wgrad3d_ws_bytes() bytes.
+ * Supported: CB <= 16, PW <= 128 and one of (kernel, CA, stride, padding):
+ *   3x3x3, CA 1,  stride 1,      no padding
+ *   3x3x3, CA 8,  stride 1 or 2, no padding
+ *   3x3x3, CA 16, stride 1 or 2, no padding;  stride 2 also with padding
+ *   5x3x3 or 4x4x4, CA 8, stride 2, no padding, CB == 8
+ * Without padding every window must lie inside `a`: (P - 1) * stride + K <= A along each axis.  Anything else returns
+ * VG_ERR_UNSUPPORTED (vg_wgrad3d_ws_bytes: -1) with vg_last_error() naming the descriptor. */
 typedef struct vg_wgrad_desc {
     int32_t N, CB, CA;
     int32_t PD, PH, PW;        /* spatial size of b */

@@ -32,8 +32,10 @@ WIDE_LAYERS = [
     ('convt4_wide', ConvSpec('convt', 8, 8, (5, 3, 3), 2), (3, 5, 12)),
     ('convt4hr_wide', ConvSpec('convt', 8, 8, (4, 4, 4), 2), (3, 3, 12)),
     ('convt5_wide', ConvSpec('convt', 8, 1, (3, 3, 3), 1), (4, 7, 13)),
-    # planes so large that ONE channel's planes fill the plane-staged kernel's LDS budget (one channel per chunk, as in the 41x49x35
-    # network's large layers)
+    # large planes (36x36 / 33x33 window rows).  Their weight gradients run on the row-walking kernel like every other case, with tiles
+    # ONE position row high (3 planes deep) and so 36 / 16 row blocks per plane: convt5_split's single window channel in the general
+    # k-step loop (rows of 36 = 9 k-steps in blocks of 3), convt4_split with the plane-shift packing, its 8 window channels resident,
+    # rows of 16 = one block of 4 k-steps
     ('convt5_split', ConvSpec('convt', 3, 1, (3, 3, 3), 1), (4, 36, 36)),
     ('convt4_split', ConvSpec('convt', 8, 8, (5, 3, 3), 2), (3, 16, 16)),
     # 33 positions per row (the first and the last layer of the 41x49x35 network): the weight-gradient rows as three compile-time blocks

@@ -149,3 +149,58 @@ def test_layer_both_engines(name, spec, isz, use_mm, monkeypatch):
     launches run in production), 2 = vg_conv_mm wherever a plan exists (also the plans mm_wins declines)"""
     monkeypatch.setattr(ops, 'USE_MM', use_mm)
     K.run_layer_case('cpu', name, spec, isz, **_layer_args(name, spec))
+
+
+class _WsQuery(Exception):
+    """carries what vg_wgrad3d_ws_bytes answered for the descriptor ops.conv_weight_grad built"""
+
+
+@pytest.fixture(scope='module')
+def wgrad_ws_query(emu_lib):
+    """query(spec, isz, N) -> (bytes or -1, vg_last_error()) for the descriptor that ops.conv_weight_grad ITSELF builds for the layer:
+    it is called on shape-only tensors through a handle of the host library whose workspace query ends the call (nothing is
+    allocated or launched)."""
+    import emu_inject
+
+    class QueryOnly(emu_inject.EmuLibrary):
+        def size(self, name, *args):
+            assert name == 'vg_wgrad3d_ws_bytes'
+            raise _WsQuery(getattr(self.dll, name)(*args), self.dll.vg_last_error().decode())
+
+    emu = _lib.get_lib()
+    handle = QueryOnly(emu.path)
+
+    def query(spec, isz, N):
+        x = torch.empty((N, spec.ci) + tuple(isz), device='meta')
+        dy = torch.empty((N, spec.co) + tuple(spec.out_size(isz)), device='meta')
+        _lib._LIB = handle
+        try:
+            with pytest.raises(_WsQuery) as q:
+                ops.conv_weight_grad(x, dy, spec, relu_in=True)
+        finally:
+            _lib._LIB = emu
+        return q.value.args
+    return query
+
+
+@pytest.mark.parametrize('img', [(41, 49, 35), (82, 98, 70), (21, 21, 21)], ids=lambda s: '%dx%dx%d' % s)
+def test_wgrad_has_an_instance_for_every_layer_of_every_geometry(img, wgrad_ws_query, monkeypatch):
+    """every weight-gradient descriptor the three networks produce is inside vg_wgrad3d's supported set (a workspace size comes
+    back), and so is the grouped query for the last decoder stage"""
+    from vae_gam_amd.schema import net_geometry
+    g = net_geometry(img)
+    monkeypatch.setattr(ops, '_GROUPED_OK', {})
+    for N in (2, 64):
+        for spec, isz in list(zip(g.enc, g.enc_sizes())) + list(zip(g.dec, g.dec_sizes())):
+            nbytes, err = wgrad_ws_query(spec, isz, N)
+            assert nbytes >= 0, (img, spec.name, N, err)
+        assert ops._grouped_wgrad_ok((N, g.nf) + tuple(g.dec_sizes()[-2]), N // 2), (img, N)
+
+
+@pytest.mark.parametrize('spec,isz', [
+    (ops.ConvSpec('convt', 8, 8, (3, 3, 3), 1, (1, 1, 1)), (5, 7, 6)),      # stride 1 with padding: no line of the instance table
+    (ops.ConvSpec('conv', 1, 8, (3, 3, 3), 1), (4, 5, 131)),                # rows of 129 positions: PW > 128
+], ids=['stride1_padded', 'pw129'])
+def test_wgrad_outside_the_supported_set_is_refused(spec, isz, wgrad_ws_query):
+    nbytes, err = wgrad_ws_query(spec, isz, 2)
+    assert nbytes == -1 and err.startswith('vg_wgrad3d'), (nbytes, err)
