@@ -416,6 +416,40 @@ int vg_adam_advance_guarded(double* state, double lr, double b1, double b2, cons
 int vg_adam_step_guarded(void* p, const void* g, void* m, void* v, int64_t n, int32_t is_f64,
                          double b1, double b2, double eps, const double* step_scalars, const double* guard, void* stream);
 
+/* Device-resident input path (an extension; the reference re-reads the whole 4-D NIfTI of a subject for every sample,
+ * DataClass_GP.py:48-51): one launch assembles the minibatch x[B][X][Y][Z] (fp32, C-contiguous, what forward_core takes) for B rows
+ * of a data set straight from the raw payloads of the subject files, kept in HBM exactly AS THEY SIT ON DISK (no host transposition,
+ * no host conversion) in one byte arena.
+ *   files    [#files] vg_vol_file (device): where a file's payload starts in the arena and how to read it.  Element (x, y, z, t) of
+ *            the file is the `dtype` value at arena + offset + (x*sx + y*sy + z*sz + t*st) * sizeof(dtype); the only alignment assumed
+ *            is that of the element itself (offset a multiple of the element size).  NIfTI is Fortran order (1, X, XY, XYZ); a C-order
+ *            .npy of shape (X, Y, Z, T) is (YZT, ZT, T, 1).
+ *   row_file, row_vol [N] int32 (device): the file and the volume t of data-set row i;  idx [B] int64 (device): the rows wanted.
+ *   x[b] = volume row_vol[idx[b]] of file row_file[idx[b]].  Nothing is clamped: the caller validates idx, row_file and row_vol.
+ *   dtype    the NIfTI datatype code every file of the table shares (2 u1, 4 i2, 8 i4, 16 f4, 64 f8, 256 i1, 512 u2, 768 u4), or 0 when
+ *            the files differ and each descriptor's own code is read; any other value returns VG_ERR_ARG.
+ * Arithmetic (a contract: bit for bit what the host path read_nifti1 -> FMRIDataset.__getitem__ -> ToTensor computes under numpy 2
+ * promotion rules; raw = the stored value, byte-swapped first when `swap` is set):
+ *   f4 files, everything in fp32:   v = raw;  if scale: v = fl32(fl32(v * (float)slope) + (float)inter)  (two roundings, never fused);
+ *                                   x = fl32(v / (float)divisor)               (IEEE division, not a multiplication by a reciprocal)
+ *   every other dtype, in fp64:     v = (double)raw;  if scale: v = fl64(fl64(v * slope) + inter);  x = (float)(v / divisor)
+ *   `scale` is the reader's own predicate, evaluated by the caller: (slope not in {0, 1} or inter != 0) and slope != 0.
+ *   Subnormal results and NaN payloads are outside the contract.
+ * Files whose x axis is the faster one (x stride below z stride: NIfTI) are staged through LDS, all x and all z of a few y per workgroup, so
+ * that both the loads and the stores of a wavefront are contiguous runs; other layouts (and shapes whose tile does not fit) are read
+ * in output order. */
+typedef struct vg_vol_file {
+    int64_t offset;            /* byte offset of the payload in the arena */
+    int64_t sx, sy, sz, st;    /* element strides of x, y, z, t */
+    double  slope, inter;      /* scl_slope, scl_inter */
+    int32_t dtype;             /* NIfTI datatype code */
+    int32_t swap;              /* 1: stored big-endian */
+    int32_t scale;             /* 1: apply v * slope + inter */
+    int32_t reserved;
+} vg_vol_file;
+int vg_volume_gather(const void* arena, const vg_vol_file* files, const int32_t* row_file, const int32_t* row_vol, const int64_t* idx,
+                     int32_t B, int32_t X, int32_t Y, int32_t Z, int32_t dtype, double divisor, float* x, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -10,6 +10,7 @@ whole synthetic or pre-loaded set in HBM so the train loop never touches the hos
 import gzip
 import os
 import struct
+import warnings
 
 import numpy as np
 import pandas as pd
@@ -19,33 +20,55 @@ from torch.utils.data import DataLoader, Dataset
 GLOBAL_MAX = 3284.5       # DataClass_GP.py:49
 
 
+NIFTI_DTYPES = {2: 'u1', 4: 'i2', 8: 'i4', 16: 'f4', 64: 'f8', 256: 'i1', 512: 'u2', 768: 'u4'}
+
+
+def _nifti1_header(head, path):
+    """Fields of a NIfTI-1 header (its first 348 bytes) that the readers use."""
+    if len(head) >= 348 and struct.unpack('<i', head[:4])[0] == 348:
+        en = '<'
+    elif len(head) >= 348 and struct.unpack('>i', head[:4])[0] == 348:
+        en = '>'
+    else:
+        raise ValueError('%s: not a NIfTI-1 file' % path)
+    dim = struct.unpack(en + '8h', head[40:56])
+    datatype, bitpix = struct.unpack(en + '2h', head[70:74])
+    vox_offset = int(struct.unpack(en + 'f', head[108:112])[0])
+    slope, inter = struct.unpack(en + '2f', head[112:120])
+    if datatype not in NIFTI_DTYPES:
+        raise ValueError('%s: unsupported NIfTI datatype %d' % (path, datatype))
+    shape = tuple(int(d) for d in dim[1:1 + dim[0]])
+    # scl_slope / scl_inter apply unless they are the identity or slope is 0 ("no scaling" in the standard)
+    scale = (slope not in (0.0, 1.0) or inter != 0.0) and slope != 0.0
+    return {'endian': en, 'shape': shape, 'dtype': datatype, 'offset': max(vox_offset, 352), 'slope': slope, 'inter': inter,
+            'scale': scale}
+
+
+def read_nifti1_raw(path):
+    """The payload of a NIfTI-1 file (.nii / .nii.gz, single file) as it sits on disk, untouched: dict(payload = a memoryview of the
+    voxel bytes (Fortran order, shape dim[1..ndim]), shape, dtype (the NIfTI code, a key of NIFTI_DTYPES), endian ('<' or '>'),
+    slope, inter, scale (whether read_nifti1 applies slope and inter)).  What ResidentVolumes uploads."""
+    opener = gzip.open if path.endswith('.gz') else open
+    with opener(path, 'rb') as f:
+        raw = f.read()
+    h = _nifti1_header(raw[:348], path)
+    nbytes = int(np.prod(h['shape'])) * np.dtype(NIFTI_DTYPES[h['dtype']]).itemsize
+    if len(raw) < h['offset'] + nbytes:
+        raise ValueError('%s: file ends before its %d voxel bytes' % (path, nbytes))
+    h['payload'] = memoryview(raw)[h['offset']:h['offset'] + nbytes]
+    del h['offset']
+    return h
+
+
 def read_nifti1(path):
     """Minimal NIfTI-1 reader (.nii / .nii.gz, single file): returns the data array in file
     order (Fortran layout -> shape dim[1..ndim]) with scl_slope/scl_inter applied.  nibabel is
     not available in the image; the reference goes through nib.load(...).dataobj."""
-    opener = gzip.open if path.endswith('.gz') else open
-    with opener(path, 'rb') as f:
-        raw = f.read()
-    if struct.unpack('<i', raw[:4])[0] == 348:
-        en = '<'
-    elif struct.unpack('>i', raw[:4])[0] == 348:
-        en = '>'
-    else:
-        raise ValueError('%s: not a NIfTI-1 file' % path)
-    dim = struct.unpack(en + '8h', raw[40:56])
-    datatype, bitpix = struct.unpack(en + '2h', raw[70:74])
-    vox_offset = int(struct.unpack(en + 'f', raw[108:112])[0])
-    slope, inter = struct.unpack(en + '2f', raw[112:120])
-    dtypes = {2: 'u1', 4: 'i2', 8: 'i4', 16: 'f4', 64: 'f8', 256: 'i1', 512: 'u2', 768: 'u4'}
-    if datatype not in dtypes:
-        raise ValueError('%s: unsupported NIfTI datatype %d' % (path, datatype))
-    shape = tuple(int(d) for d in dim[1:1 + dim[0]])
-    n = int(np.prod(shape))
-    a = np.frombuffer(raw, dtype=np.dtype(en + dtypes[datatype]), count=n, offset=max(vox_offset, 352))
-    a = a.reshape(shape, order='F')
-    if slope not in (0.0, 1.0) or inter != 0.0:
-        if slope != 0.0:
-            a = a * slope + inter
+    h = read_nifti1_raw(path)
+    a = np.frombuffer(h['payload'], dtype=np.dtype(h['endian'] + NIFTI_DTYPES[h['dtype']]))
+    a = a.reshape(h['shape'], order='F')
+    if h['scale']:
+        a = a * h['slope'] + h['inter']
     return a
 
 
@@ -100,9 +123,17 @@ class ToTensor(object):
                 'vol_num': torch.tensor(sample['vol_num'], dtype=torch.float64)}
 
 
-def setup_data_loaders(batch_size=32, shuffle=(True, False, False), train_csv='', test_csv='', prefetch_device=None):
+def setup_data_loaders(batch_size=32, shuffle=(True, False, False), train_csv='', test_csv='', prefetch_device=None,
+                       resident_device=None):
     """{'Shuffled_train', 'UnShuffled_train', 'test'} loaders (DataClass_GP.py:73-89).
-    prefetch_device (extension): a CUDA device -> the loaders collate into pinned host memory and are wrapped in DevicePrefetcher."""
+    prefetch_device (extension): a CUDA device -> the loaders collate into pinned host memory and are wrapped in DevicePrefetcher.
+    resident_device (extension): a device -> every subject file is uploaded once (ResidentVolumes) and the three loaders are
+    ResidentLoaders over it: the same minibatches in the same order, assembled on the device."""
+    if resident_device is not None:
+        vols = ResidentVolumes([train_csv, test_csv], resident_device)
+        mk = lambda view, sh: ResidentLoader(view, index_batches(len(view), batch_size, sh))
+        return {'Shuffled_train': mk(vols.views[0], shuffle[0]), 'UnShuffled_train': mk(vols.views[0], shuffle[1]),
+                'test': mk(vols.views[1], shuffle[2])}
     train_dataset = FMRIDataset(csv_file=train_csv, transform=ToTensor())
     test_dataset = FMRIDataset(csv_file=test_csv, transform=ToTensor())
     pin = prefetch_device is not None and torch.device(prefetch_device).type == 'cuda'
@@ -181,3 +212,179 @@ class DeviceResidentData:
             idx = idx[self.rank * local:(self.rank + 1) * local].to(self.volumes.device)
             yield {'volume': self.volumes[idx], 'covariates': self.covariates[idx], 'subjid': self.subjid[idx],
                    'vol_num': idx.double()}
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# Device-resident input path (extension): the subject files themselves live in HBM and a HIP kernel assembles every minibatch from
+# an index list (include/vaegam.h: vg_volume_gather).  DeviceResidentData above needs the decoded fp32 volumes handed in; this path
+# starts from the CSV of NIfTI / .npy files that the file loaders read, and yields bit for bit what they yield.
+
+ARENA_ALIGN = 256
+_NPY_DTYPES = {('u', 1): 2, ('i', 2): 4, ('i', 4): 8, ('f', 4): 16, ('f', 8): 64, ('i', 1): 256, ('u', 2): 512, ('u', 4): 768}
+# one entry of the descriptor table: vg_vol_file of include/vaegam.h
+VOL_FILE_DTYPE = np.dtype([('offset', '<i8'), ('sx', '<i8'), ('sy', '<i8'), ('sz', '<i8'), ('st', '<i8'), ('slope', '<f8'), ('inter', '<f8'),
+                           ('dtype', '<i4'), ('swap', '<i4'), ('scale', '<i4'), ('reserved', '<i4')])
+
+
+def _probe_volume_file(path):
+    """What the descriptor of a 4-D subject file needs, without reading its voxels: dict(shape, dtype code, itemsize, swap,
+    strides (elements), slope, inter, scale)."""
+    if path.endswith('.npy'):
+        a = np.load(path, mmap_mode='r')
+        code = _NPY_DTYPES.get((a.dtype.kind, a.dtype.itemsize))
+        if code is None:
+            raise ValueError('%s: dtype %s is not one the volume gather reads (%s)' % (path, a.dtype, ', '.join(sorted(NIFTI_DTYPES.values()))))
+        if a.ndim != 4:
+            raise ValueError('%s: expected a 4-D array (X, Y, Z, T), got shape %s' % (path, a.shape))
+        if a.flags.f_contiguous and not a.flags.c_contiguous:
+            strides = tuple(int(np.prod(a.shape[:k])) for k in range(4))
+        else:                                                    # C order as stored, or what the contiguous copy will be
+            strides = tuple(int(np.prod(a.shape[k + 1:])) for k in range(4))
+        big = a.dtype.byteorder == '>' or (a.dtype.byteorder == '=' and not np.little_endian)
+        return {'shape': tuple(a.shape), 'dtype': code, 'itemsize': a.dtype.itemsize, 'swap': big and a.dtype.itemsize > 1, 'strides': strides,
+                'slope': 1.0, 'inter': 0.0, 'scale': False}
+    opener = gzip.open if path.endswith('.gz') else open
+    with opener(path, 'rb') as f:
+        h = _nifti1_header(f.read(348), path)
+    if len(h['shape']) != 4:
+        raise ValueError('%s: expected a 4-D NIfTI (X, Y, Z, T), got shape %s' % (path, h['shape']))
+    itemsize = np.dtype(NIFTI_DTYPES[h['dtype']]).itemsize
+    return {'shape': h['shape'], 'dtype': h['dtype'], 'itemsize': itemsize, 'swap': h['endian'] == '>' and itemsize > 1,
+            'strides': tuple(int(np.prod(h['shape'][:k])) for k in range(4)), 'slope': h['slope'], 'inter': h['inter'],
+            'scale': bool(h['scale'])}
+
+
+def _volume_file_bytes(path):
+    """The voxel bytes of a subject file as a flat uint8 array, in the layout _probe_volume_file described."""
+    if path.endswith('.npy'):
+        a = np.load(path, mmap_mode='r')
+        if a.flags.f_contiguous and not a.flags.c_contiguous:
+            a = a.T                                              # the same bytes, seen in C order
+        return np.ascontiguousarray(a).reshape(-1).view(np.uint8)
+    return np.frombuffer(read_nifti1_raw(path)['payload'], dtype=np.uint8)
+
+
+class ResidentView:
+    """The rows of one CSV over a ResidentVolumes arena: which file and volume each row is, and the row's small tensors, all on the
+    device.  It stands in for the data set of a loader (`len()`, `.df`)."""
+
+    def __init__(self, volumes, csv_file, df, row_file, row_vol):
+        dev = volumes.device
+        self.volumes, self.csv_file, self.df = volumes, csv_file, df
+        self.row_file = torch.from_numpy(row_file.astype(np.int32)).to(dev)
+        self.row_vol = torch.from_numpy(row_vol.astype(np.int32)).to(dev)
+        self.covariates = torch.from_numpy(df.iloc[:, 4:12].to_numpy(dtype=np.float64)).float().to(dev)      # = ToTensor
+        self.subjid = torch.from_numpy(pd.factorize(df.iloc[:, 1])[0].astype(np.int64)).to(dev)              # first-appearance order of THIS csv
+        self.vol_num = torch.from_numpy(df.iloc[:, 2].to_numpy(dtype=np.float64)).to(dev)
+
+    def __len__(self):
+        return len(self.df)
+
+    def batch(self, idx):
+        """The sample dictionary of rows `idx` (int64 tensor on the device, already validated)."""
+        from . import ops
+        v = self.volumes
+        x = ops.volume_gather(v.arena, v.files, self.row_file, self.row_vol, idx, v.shape, v.dtype, GLOBAL_MAX)
+        return {'covariates': self.covariates.index_select(0, idx), 'volume': x, 'subjid': self.subjid.index_select(0, idx),
+                'vol_num': self.vol_num.index_select(0, idx)}
+
+
+class ResidentVolumes:
+    """Every distinct subject file named by `csv_files` (column 3, nii_path), decoded never and uploaded once: the raw payloads sit
+    in one byte arena on `device`, each starting on a 256-byte boundary, next to a table that says how to read them (dtype, byte
+    order, element strides, scl_slope / scl_inter).  `.views[i]` is the ResidentView of csv_files[i]; a file named by several CSVs
+    is held once.  .npy files keep their own layout when C- or F-contiguous.  Raises ValueError naming the file for a dtype the
+    gather does not read, a file that is not 4-D, a spatial shape that differs between files or a volume number outside its file,
+    and -- before anything is allocated -- when the arena would exceed `max_bytes` (default: half of the free device memory)."""
+
+    def __init__(self, csv_files, device, max_bytes=None):
+        from . import _lib
+        self.device = torch.device(device)
+        if self.device.type != 'cuda' and not _lib.get_lib().host_pointers_ok:
+            raise RuntimeError('ResidentVolumes needs a GPU device: the HIP kernels need device pointers (no CPU path)')
+        frames = [pd.read_csv(c) for c in csv_files]
+        paths = list(dict.fromkeys(p for df in frames for p in df.iloc[:, 3].tolist()))
+        self.paths = paths
+        info, offsets, total = [], [], 0
+        for p in paths:
+            m = _probe_volume_file(p)
+            if info and m['shape'][:3] != info[0]['shape'][:3]:
+                raise ValueError('%s: spatial shape %s differs from %s of %s' % (p, m['shape'][:3], info[0]['shape'][:3], paths[0]))
+            info.append(m)
+            offsets.append(total)
+            total += -(-int(np.prod(m['shape'])) * m['itemsize'] // ARENA_ALIGN) * ARENA_ALIGN
+        if max_bytes is None and self.device.type == 'cuda':
+            max_bytes = torch.cuda.mem_get_info(self.device)[0] // 2
+        if max_bytes is not None and total > max_bytes:
+            raise ValueError('the %d subject files need %d bytes of device memory, more than the %d allowed (max_bytes); '
+                             'use the file loaders for this data set' % (len(paths), total, max_bytes))
+        self.shape = tuple(info[0]['shape'][:3]) if info else (0, 0, 0)
+        self.nbytes = total
+        codes = {m['dtype'] for m in info}
+        self.dtype = codes.pop() if len(codes) == 1 else 0       # one code for the whole table, or 0: read each descriptor's
+        table = np.zeros(len(paths), dtype=VOL_FILE_DTYPE)
+        self.arena = torch.empty(max(total, 1), dtype=torch.uint8, device=self.device)
+        for k, (p, m) in enumerate(zip(paths, info)):
+            raw = _volume_file_bytes(p)
+            assert raw.size == int(np.prod(m['shape'])) * m['itemsize'], p
+            with warnings.catch_warnings():
+                warnings.simplefilter('ignore', UserWarning)     # read-only buffer: it is only copied from
+                self.arena[offsets[k]:offsets[k] + raw.size].copy_(torch.from_numpy(raw))
+            table[k] = (offsets[k],) + m['strides'] + (m['slope'], m['inter'], m['dtype'], int(m['swap']), int(m['scale']), 0)
+        self.files = torch.from_numpy(table.view(np.uint8).reshape(len(paths), -1)).to(self.device)
+        index = {p: k for k, p in enumerate(paths)}
+        self.views = []
+        for c, df in zip(csv_files, frames):
+            row_file = df.iloc[:, 3].map(index).to_numpy(dtype=np.int64)
+            row_vol = df.iloc[:, 2].to_numpy(dtype=np.int64)
+            n_t = np.array([m['shape'][3] for m in info], dtype=np.int64)[row_file] if len(df) else row_vol
+            bad = np.nonzero((row_vol < 0) | (row_vol >= n_t))[0]
+            if bad.size:
+                r = int(bad[0])
+                raise ValueError('%s row %d: volume %d is outside %s (%d volumes)' % (c, r, row_vol[r], paths[row_file[r]], n_t[r]))
+            self.views.append(ResidentView(self, c, df, row_file, row_vol))
+
+
+class _RowIndices(Dataset):
+    """The row numbers 0..n-1 as a data set: a DataLoader over it draws its seeds and shuffles exactly as one over FMRIDataset."""
+
+    def __init__(self, n):
+        self.n = int(n)
+
+    def __len__(self):
+        return self.n
+
+    def __getitem__(self, i):
+        return i
+
+
+def index_batches(n, batch_size, shuffle):
+    """The minibatches of a DataLoader(dataset of n rows, batch_size, shuffle) as int64 index tensors: the same order under the same
+    torch.manual_seed, epoch after epoch, and the same draws from the CPU generator."""
+    return DataLoader(_RowIndices(n), batch_size=batch_size, shuffle=shuffle, num_workers=0,
+                      collate_fn=lambda rows: torch.tensor(rows, dtype=torch.int64))
+
+
+class ResidentLoader:
+    """Minibatches of a ResidentView: iterates `batch_sampler` (anything that yields the row numbers of one minibatch at a time as a
+    list or an int64 tensor: index_batches, dp.ShardedBatchSampler), copies the B indices to the device -- the only host work per
+    batch -- and yields the sample dictionary of the file loaders ('covariates', 'volume', 'subjid', 'vol_num'; same dtypes and
+    shapes) with every tensor on the device."""
+
+    def __init__(self, view, batch_sampler):
+        self.view, self.batch_sampler = view, batch_sampler
+        self.dataset = view                                      # len(loader.dataset) and .df as the train loop uses them
+
+    def __len__(self):
+        return len(self.batch_sampler)
+
+    def __iter__(self):
+        n, dev = len(self.view), self.view.volumes.device
+        for rows in self.batch_sampler:
+            idx = torch.as_tensor(rows, dtype=torch.int64)
+            if idx.ndim != 1 or idx.numel() == 0:
+                raise ValueError('ResidentLoader: a minibatch is a non-empty list of row numbers, got shape %s' % (tuple(idx.shape),))
+            if int(idx.min()) < 0 or int(idx.max()) >= n:
+                raise IndexError('ResidentLoader: row numbers %d..%d are outside the %d rows of %s'
+                                 % (int(idx.min()), int(idx.max()), n, self.view.csv_file))
+            yield self.view.batch(idx.to(dev, non_blocking=True))

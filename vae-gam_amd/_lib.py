@@ -48,6 +48,11 @@ class FcJob(ctypes.Structure):
     _fields_ = [('d', FcDesc), ('A', vp), ('amask', vp), ('B', vp), ('bias', vp), ('cmask', vp), ('C', vp), ('cx', vp), ('ws', vp)]
 
 
+class VolFile(ctypes.Structure):
+    _fields_ = [('offset', i64), ('sx', i64), ('sy', i64), ('sz', i64), ('st', i64), ('slope', f64), ('inter', f64),
+                ('dtype', i32), ('swap', i32), ('scale', i32), ('reserved', i32)]
+
+
 FC_A_RELU, FC_A_MASK, FC_B_RELU, FC_B_ONES, FC_C_BIAS, FC_C_RELU, FC_C_MASK, FC_C_ACCUM = 1, 2, 4, 8, 16, 32, 64, 128
 
 
@@ -106,6 +111,7 @@ _PROTOS = {
     'vg_grad_guard': (ctypes.c_int, [vp, i64, vp, i64, f64, i32, vp, vp, vp]),
     'vg_adam_advance_guarded': (ctypes.c_int, [vp, f64, f64, f64, vp, vp]),
     'vg_adam_step_guarded': (ctypes.c_int, [vp, vp, vp, vp, i64, i32, f64, f64, f64, vp, vp, vp]),
+    'vg_volume_gather': (ctypes.c_int, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, f64, vp, vp]),
 }
 GUARD_STATE_LEN = 8            # VG_GUARD_STATE_LEN: [total_norm, scale, apply, seen, skipped, clipped, norm_sum, norm_max]
 EXPORTS = tuple(_PROTOS)

@@ -446,3 +446,140 @@ extern "C" int vg_umap_layout_epoch(const int32_t* rowptr, const int32_t* col, c
               (int)n_epochs, (float)a, (float)b, (int)negative_sample_rate, seed, y_out);
     return vg_check_launch("umap_layout_epoch");
 }
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// Device-resident input path (an extension; include/vaegam.h: vg_volume_gather): the minibatch x[B][X][Y][Z] assembled in one launch
+// from the raw payloads of the subject files, kept in HBM as they sit on disk.  Not part of the captured step: it fills the tensor the
+// step's graph copies in.
+//
+// A workgroup owns the slab (all x, TY consecutive y, all z) of one volume.  NIfTI is x-fastest, the output z-fastest; for a fixed z the
+// source of the slab is one contiguous run over (x, y) and for a fixed x its destination is one contiguous run over (y, z), so staging
+// the converted slab in LDS makes both the loads and the stores of a wavefront contiguous.  LDS element (x, q = yy*Z + z) sits at
+// q*P + x with P odd: the store phase reads it with consecutive lanes on consecutive q -- a stride of P words, conflict-free -- and the
+// load phase writes runs of consecutive x.  Files that are not x-fastest (a C-order .npy has t, then z fastest) gain nothing from the
+// transposition and are read in output order, as are shapes whose slab does not fit in LDS even at TY = 1.
+#include "../../include/vaegam.h"
+
+namespace {
+
+constexpr int VOLG_LDS_BYTES = 32 * 1024;   // slab budget: 5 workgroups per CU
+constexpr int VOLG_TY_MAX = 8;
+
+__host__ __device__ static inline int volg_esize(int dt) {
+    return (dt == 2 || dt == 256) ? 1 : (dt == 4 || dt == 512) ? 2 : dt == 64 ? 8 : 4;
+}
+
+// one stored element -> the fp32 value the host path computes for it (the arithmetic contract of include/vaegam.h).  DT: the dtype code
+// when the whole table shares one (the switch folds away), 0: the descriptor's.
+template <int DT>
+__device__ __forceinline__ float volg_value(const unsigned char* p, int dt_file, int swap, int scale, double slope, double inter, double divisor) {
+#pragma clang fp contract(off)
+    const int dt = DT ? DT : dt_file;
+    if (dt == 16) {
+        union { uint32_t u; float f; } t;
+        t.u = *reinterpret_cast<const uint32_t*>(p);
+        if (swap) t.u = __builtin_bswap32(t.u);
+        float v = t.f;
+        if (scale) { v = v * (float)slope; v = v + (float)inter; }
+        return v / (float)divisor;
+    }
+    double v;
+    switch (dt) {
+        case 2: v = (double)*p; break;
+        case 256: v = (double)*reinterpret_cast<const int8_t*>(p); break;
+        case 4: case 512: {
+            uint16_t u = *reinterpret_cast<const uint16_t*>(p);
+            if (swap) u = __builtin_bswap16(u);
+            v = dt == 4 ? (double)(int16_t)u : (double)u;
+        } break;
+        case 8: case 768: {
+            uint32_t u = *reinterpret_cast<const uint32_t*>(p);
+            if (swap) u = __builtin_bswap32(u);
+            v = dt == 8 ? (double)(int32_t)u : (double)u;
+        } break;
+        default: {                                       // 64
+            union { uint64_t u; double f; } t;
+            t.u = *reinterpret_cast<const uint64_t*>(p);
+            if (swap) t.u = __builtin_bswap64(t.u);
+            v = t.f;
+        } break;
+    }
+    if (scale) { v = v * slope; v = v + inter; }
+    return (float)(v / divisor);
+}
+
+// block = (volume b, y tile): ntile = ceil(Y / TY) tiles per volume.  P: LDS pitch (odd, >= X), 0 = no LDS slab (read in output order).
+template <int DT>
+__global__ void __launch_bounds__(256)
+volume_gather_k(const unsigned char* __restrict__ arena, const vg_vol_file* __restrict__ files, const int32_t* __restrict__ row_file,
+                const int32_t* __restrict__ row_vol, const int64_t* __restrict__ idx, int X, int Y, int Z, int TY, int P, int ntile,
+                double divisor, float* __restrict__ out) {
+    VG_DYN_SMEM(float, tile);
+    const int tid = threadIdx.x, nt = blockDim.x;
+    const int b = blockIdx.x / ntile, y0 = (blockIdx.x - b * ntile) * TY, ty = min(TY, Y - y0);
+    const int64_t row = idx[b];
+    const vg_vol_file f = files[row_file[row]];
+    const int64_t es = volg_esize(DT ? DT : f.dtype);
+    const unsigned char* src = arena + f.offset + ((int64_t)row_vol[row] * f.st + (int64_t)y0 * f.sy) * es;
+    float* dst = out + ((size_t)b * X * Y + y0) * Z;     // element (x, yy, z) of the slab: dst[x*Y*Z + yy*Z + z]
+    const int nq = ty * Z, n = X * nq;
+    const size_t YZ = (size_t)Y * Z;
+    if (P > 0 && f.sx < f.sz) {
+        const int nr = ty * X;                           // for a fixed z: (yy, x) is one run of the file when sy = X*sx
+#pragma unroll 4
+        for (int e = tid; e < n; e += nt) {
+            const int z = e / nr, r = e - z * nr, yy = r / X, xx = r - yy * X;
+            tile[(yy * Z + z) * P + xx] = volg_value<DT>(src + (xx * f.sx + yy * f.sy + z * f.sz) * es, f.dtype, f.swap, f.scale, f.slope,
+                                                         f.inter, divisor);
+        }
+        __syncthreads();
+        for (int e = tid; e < n; e += nt) {
+            const int xx = e / nq, q = e - xx * nq;
+            dst[xx * YZ + q] = tile[q * P + xx];
+        }
+    } else {
+#pragma unroll 4
+        for (int e = tid; e < n; e += nt) {
+            const int xx = e / nq, q = e - xx * nq, yy = q / Z, z = q - yy * Z;
+            dst[xx * YZ + q] = volg_value<DT>(src + (xx * f.sx + yy * f.sy + z * f.sz) * es, f.dtype, f.swap, f.scale, f.slope, f.inter,
+                                              divisor);
+        }
+    }
+}
+
+template <int DT>
+void volg_launch(int grid, size_t shmem, hipStream_t s, const void* arena, const vg_vol_file* files, const int32_t* row_file,
+                 const int32_t* row_vol, const int64_t* idx, int X, int Y, int Z, int TY, int P, int ntile, double divisor, float* x) {
+    vg_launch(volume_gather_k<DT>, dim3(grid), dim3(256), shmem, s, (const unsigned char*)arena, files, row_file, row_vol, idx, X, Y, Z,
+              TY, P, ntile, divisor, x);
+}
+
+}  // namespace
+
+extern "C" int vg_volume_gather(const void* arena, const vg_vol_file* files, const int32_t* row_file, const int32_t* row_vol,
+                                const int64_t* idx, int32_t B, int32_t X, int32_t Y, int32_t Z, int32_t dtype, double divisor, float* x,
+                                void* stream) {
+    if (!arena || !files || !row_file || !row_vol || !idx || !x) { vg_set_error("vg_volume_gather: null argument"); return VG_ERR_ARG; }
+    if (B <= 0 || X <= 0 || Y <= 0 || Z <= 0 || (int64_t)X * Z > (1 << 27) || !(divisor != 0.0)) {
+        vg_set_error("vg_volume_gather: bad argument (B %d, volume %d x %d x %d, divisor %g)", B, X, Y, Z, divisor);
+        return VG_ERR_ARG;
+    }
+    int P = X | 1;                                       // odd pitch
+    const int64_t per_y = (int64_t)Z * P * (int64_t)sizeof(float);
+    int TY = (int)(VOLG_LDS_BYTES / per_y);
+    if (TY < 1) P = 0;                                   // not even one y fits: no slab
+    if (TY < 1 || TY > VOLG_TY_MAX) TY = VOLG_TY_MAX;
+    if (TY > Y) TY = Y;
+    const int ntile = vg_cdiv(Y, TY);
+    if ((int64_t)ntile * B > INT_MAX) { vg_set_error("vg_volume_gather: B %d x %d tiles exceeds the grid", B, ntile); return VG_ERR_ARG; }
+    const int grid = ntile * B;
+    const size_t shmem = (size_t)TY * Z * P * sizeof(float);
+    hipStream_t s = (hipStream_t)stream;
+#define VOLG_CASE(DT) case DT: volg_launch<DT>(grid, shmem, s, arena, files, row_file, row_vol, idx, X, Y, Z, TY, P, ntile, divisor, x); break
+    switch (dtype) {
+        VOLG_CASE(0); VOLG_CASE(2); VOLG_CASE(4); VOLG_CASE(8); VOLG_CASE(16); VOLG_CASE(64); VOLG_CASE(256); VOLG_CASE(512); VOLG_CASE(768);
+        default: vg_set_error("vg_volume_gather: unknown dtype code %d", dtype); return VG_ERR_ARG;
+    }
+#undef VOLG_CASE
+    return vg_check_launch("volume_gather");
+}

@@ -95,13 +95,18 @@ class DataParallelContext:
     def shard_loaders(self, loaders, global_batch, seed):
         """The DataLoaders of DataClass_GP.setup_data_loaders re-built so that every rank draws ITS slice of every global
         minibatch: same data sets, `ShardedBatchSampler` instead of the per-process shuffling (which, seeded identically on
-        every rank, would hand all ranks the same samples)."""
+        every rank, would hand all ranks the same samples).  Device-resident loaders (DataClass_GP.ResidentLoader) are re-built
+        over the same view: every rank holds the WHOLE arena of subject files in its own HBM and gathers only its slice."""
         from torch.utils.data import DataLoader
+        from .DataClass_GP import ResidentLoader
         out = {}
         for name, ld in loaders.items():
             sampler = ShardedBatchSampler(len(ld.dataset), global_batch, self.rank, self.world_size,
                                           shuffle=(name == 'Shuffled_train'), seed=seed)
-            out[name] = DataLoader(ld.dataset, batch_sampler=sampler, num_workers=0, collate_fn=ld.collate_fn)
+            if isinstance(ld, ResidentLoader):
+                out[name] = ResidentLoader(ld.view, sampler)
+            else:
+                out[name] = DataLoader(ld.dataset, batch_sampler=sampler, num_workers=0, collate_fn=ld.collate_fn)
         return out
 
     def shutdown(self):

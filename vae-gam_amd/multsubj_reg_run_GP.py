@@ -50,6 +50,13 @@ def build_parser():
     parser.add_argument('--skip_nonfinite', type=str2bool, nargs='?', const=True, default=False,
                         help='(extension) Skip a step whose gradient holds an inf / nan (parameters and Adam state untouched) instead of '
                              'writing it into every parameter; skipped steps are counted and reported per epoch.')
+    parser.add_argument('--device_resident', type=str2bool, nargs='?', const=True, default=False,
+                        help='(extension) Upload every subject file once and assemble the minibatches on the GPU from an index list '
+                             '(DataClass_GP.ResidentVolumes) instead of reading them through the host loaders; the same minibatches in '
+                             'the same order.  The files must fit in half of the free device memory.')
+    parser.add_argument('--hip_graph', type=str2bool, nargs='?', const=True, default=False,
+                        help='(extension) Capture the train step into a hipGraph once per batch shape and replay it; where capture is '
+                             'refused the step runs as eager launches and says so.')
     return parser
 
 
@@ -74,14 +81,22 @@ def main(argv=None):
     # see the batches a single process would; under data parallelism the train / test loops get re-built loaders that hand each rank
     # its slice of every global minibatch (they only take the data sets from these)
     # (single process on a GPU: minibatches are staged in pinned memory and copied one batch ahead on a side stream)
-    full_loaders = data.setup_data_loaders(batch_size=args.batch_size, train_csv=args.train_csv, test_csv=args.test_csv,
-                                           prefetch_device='cuda' if (dp is None and torch.cuda.is_available()) else None)
+    # (--device_resident: the subject files live in HBM and a kernel assembles the minibatches; every rank holds all of them)
+    if args.device_resident:
+        if not torch.cuda.is_available():
+            raise SystemExit('--device_resident needs a GPU')
+        full_loaders = data.setup_data_loaders(batch_size=args.batch_size, train_csv=args.train_csv, test_csv=args.test_csv,
+                                               resident_device='cuda')
+    else:
+        full_loaders = data.setup_data_loaders(batch_size=args.batch_size, train_csv=args.train_csv, test_csv=args.test_csv,
+                                               prefetch_device='cuda' if (dp is None and torch.cuda.is_available()) else None)
     loaders_dict = full_loaders if dp is None else dp.shard_loaders(full_loaders, args.batch_size, args.seed)
     model = vae_reg.VAE(num_inducing_pts=args.num_inducing_pts, gp_kl_scale=args.gp_kl_scale,
                         glm_reg_scale=args.glm_reg_scale, glm_maps=args.glm_maps, save_dir=args.save_dir,
                         csv_files=[args.train_csv, args.test_csv], neural_covariates=args.neural_covariates,
                         data_parallel=dp, dp_gain=os.environ.get('VG_DP_GAIN', 'global'), gp_jitter=args.gp_jitter,
                         max_grad_norm=args.max_grad_norm, skip_nonfinite=args.skip_nonfinite)
+    model.use_hip_graph = bool(args.hip_graph)
     if args.from_ckpt:
         assert os.path.exists(args.ckpt_path), 'Oops, looks like ckpt file given does NOT exist!'
         print('=' * 40)

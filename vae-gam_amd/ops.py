@@ -1158,8 +1158,25 @@ def adam_step_guarded_(p, g, m, v, b1, b2, eps, step_scalars, guard):
           float(eps), _p(_chk(step_scalars, torch.float64)), _p(_chk(guard, torch.float64)))
 
 
+# --------------------------------------------------------------------------- device-resident input path (include/vaegam.h)
+def volume_gather(arena, files, row_file, row_vol, idx, shape, dtype, divisor, out=None):
+    """x (B, X, Y, Z) fp32 = the volumes of data-set rows idx (int64, B of them), read from the raw file payloads in `arena` (uint8)
+    through the descriptor table `files` (DataClass_GP.ResidentVolumes builds both) and divided by `divisor`.  dtype: the NIfTI code
+    every file shares, or 0.  The caller has validated idx, row_file and row_vol: the kernel clamps nothing."""
+    _chk(arena, torch.uint8); _chk(files, torch.uint8); _chk(row_file, torch.int32); _chk(row_vol, torch.int32); _chk(idx, torch.int64)
+    assert files.ndim == 2 and files.shape[1] == ctypes.sizeof(_lib.VolFile), 'descriptor table does not match vg_vol_file'
+    assert idx.ndim == 1 and idx.device == arena.device
+    B, (X, Y, Z) = idx.numel(), shape
+    if out is None:
+        out = torch.empty((B, X, Y, Z), dtype=torch.float32, device=arena.device)
+    assert tuple(out.shape) == (B, X, Y, Z)
+    _call(arena, 'vg_volume_gather', _p(arena), _p(files), _p(row_file), _p(row_vol), _p(idx), B, X, Y, Z, int(dtype), float(divisor),
+          _p(_chk(out)))
+    return out
+
+
 # --------------------------------------------------------------------------- matrix-core convolution plans (vg_conv_mm)
-USE_MM = int(_os.environ.get('VG_CONV_MM', '1'))            # 0: off; 1: where it measured faster (mm_wins); 2: wherever a plan exists
+USE_MM =int(_os.environ.get('VG_CONV_MM', '1'))            # 0: off; 1: where it measured faster (mm_wins); 2: wherever a plan exists
 _MM_LDS_BUDGET = 150 * 1024
 _MM_LDS_CU = 160 * 1024                                     # LDS of a CU: what co-resident blocks share
 # (mode, stride, CI, CO, kernel, read size, write size) -> (waves, PD, PHB, cc, dbuf): tools/diag/mm_sweep.py at batch 64, 8 covariates
