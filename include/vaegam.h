@@ -133,6 +133,21 @@ int64_t vg_wgrad3d_grouped_ws_bytes(const vg_wgrad_desc* d);
 int vg_wgrad3d_grouped(const vg_wgrad_desc* d, const float* a, const float* b, const float* in_scale,
                        const float* in_shift, float* ws, float* out, void* stream);
 
+/* What vg_wgrad3d (grouped != 0: vg_wgrad3d_grouped) would launch for the descriptor: nothing is launched and no tensor memory is
+ * touched.  The record comes from the planner itself, at the point where the workspace queries return.  out[0 .. VG_WGRAD_PLAN_LEN):
+ *    0 CA   1 KD   2 KH   3 KW   4 stride   5 PAD   6 DSH          the kernel family (DSH: plane-shift packing)
+ *    7 PA   8 UG   9 RES  10 GRP  11 ONE                            the instance of the family
+ *   12 TPD 13 TPH 14 nbuf                                           tile (position planes x rows), window-channel slots (CA / 2 / 1)
+ *   15 pdblocks  16 nph                                             tiles per sample along depth / rows
+ *   17 items  18 grid  19 wave_slabs                                work items, blocks, 1: one slab per wave, 0: one per block
+ *   20 ipb  21 grp_items                                            grouped: blocks per group, items per group (else 0)
+ *   22 nslabs  23 lds_bytes  24 blocks_per_cu                       slabs in the workspace, LDS per block, the occupancy answer used
+ * n_out < VG_WGRAD_PLAN_LEN, a null or malformed descriptor (non-positive sizes, stride other than 1 or 2) return VG_ERR_ARG, as
+ * vg_wgrad3d does (the workspace queries answer -1 for those too); for a well-formed descriptor the result is VG_ERR_UNSUPPORTED exactly
+ * where the matching workspace query returns -1, and VG_OK otherwise. */
+#define VG_WGRAD_PLAN_LEN 25
+int vg_wgrad3d_plan(const vg_wgrad_desc* d, int32_t grouped, int32_t* out, int32_t n_out);
+
 /* batch-norm batch statistics (BatchNorm3d(track_running_stats=False), vae_reg_GP.py:194-196,
  * 216-218): for x [N][C][P], group g = n / per_group: mean/var over (per_group samples, P) of
  * relu?(x); writes scale = gamma*rstd, shift = beta - mean*scale, mean, rstd ([G][C] each).

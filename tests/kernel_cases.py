@@ -6,7 +6,7 @@ import torch
 import torch.nn.functional as F
 
 import vae_gam_amd  # noqa: F401
-from vae_gam_amd import ops
+from vae_gam_amd import _lib, ops
 from vae_gam_amd.ops import ConvSpec
 
 # (name, spec, small input size) -- one entry per layer of vae_reg_GP.py:189-215, spatial sizes shrunk
@@ -62,7 +62,21 @@ def ref_layer(p, w, b, gamma, beta, spec, relu_in, per_group):
     return F.conv_transpose3d(h, w, b, spec.stride, spec.pad, spec.outpad)
 
 
-def run_layer_case(dev, name, spec, isz, with_bn, relu_in, groups, input_is_data=False, seed=0, tol=2e-4):
+def _bind_random_grads(params, g):
+    """nn.Parameters whose .grad is prefilled with random values r (what the optimiser's flat gradient buffer holds mid-accumulation):
+    -> [r] (CPU copies)"""
+    rs = []
+    for t in params:
+        r = 2 * torch.randn(t.shape, generator=g)
+        t.grad = r.clone().to(t.device)
+        rs.append(r)
+    return rs
+
+
+def run_layer_case(dev, name, spec, isz, with_bn, relu_in, groups, input_is_data=False, seed=0, tol=2e-4, bound_grads=False):
+    """bound_grads: weight, bias, gamma and beta are nn.Parameters with a bound, randomly prefilled .grad: the backward must add its
+    gradients straight into those buffers (the accumulate forms of vg_wgrad3d, vg_channel_sum, vg_bn_param_grad, vg_bn_tconv1_sums,
+    vg_data_bn_grads; on the GPU the side-stream branch), hand autograd None for them, and .grad - r must be the reference gradient."""
     g = torch.Generator().manual_seed(seed)
     per_group = 2
     N = per_group * groups
@@ -81,22 +95,71 @@ def run_layer_case(dev, name, spec, isz, with_bn, relu_in, groups, input_is_data
         ref_grads += [None, None]
 
     dleaves = [t.to(dev).clone().requires_grad_(True) if t is not None else None for t in (p, w, b, gamma, beta)]
+    prefill = [None] * 5
+    if bound_grads:
+        for i in range(1, 5):
+            if dleaves[i] is not None:
+                dleaves[i] = torch.nn.Parameter(dleaves[i].detach())
+        rs = iter(_bind_random_grads([t for t in dleaves[1:] if t is not None], g))
+        prefill = [None] + [None if t is None else next(rs) for t in dleaves[1:]]
     if input_is_data:
         dleaves[0] = dleaves[0].detach()
     y = ops.bn_conv_act(dleaves[0], dleaves[1], dleaves[2], dleaves[3], dleaves[4], spec, relu_in, per_group, input_is_data)
     assert y.shape == y_ref.shape, (y.shape, y_ref.shape)
     np.testing.assert_allclose(y.detach().cpu().numpy(), y_ref.detach().numpy(), rtol=tol, atol=tol, err_msg=name + ' fwd')
     ins = [t for t in dleaves if t is not None and t.requires_grad]
-    grads = list(torch.autograd.grad(y, ins, gy.to(dev)))
+    grads = list(torch.autograd.grad(y, ins, gy.to(dev), allow_unused=bound_grads))
+    if bound_grads and y.is_cuda:
+        ops.join_side_stream(y.device)
     names = ['p', 'w', 'b', 'gamma', 'beta']
     k = 0
     for i, t in enumerate(dleaves):
         if t is None or not t.requires_grad:
             continue
-        got = grads[k].cpu().numpy(); k += 1
+        got = grads[k]; k += 1
+        if bound_grads and i > 0:
+            assert got is None, '%s d%s: autograd was handed a tensor although .grad is bound' % (name, names[i])
+            got = t.grad.cpu() - prefill[i]
+        got = got.cpu().numpy()
         want = ref_grads[i].numpy()
         scale = max(1.0, float(np.abs(want).max()))
         np.testing.assert_allclose(got, want, rtol=5 * tol, atol=5 * tol * scale, err_msg='%s d%s' % (name, names[i]))
+
+
+def run_chain_case(dev, isz=(3, 4, 5), groups=2, per_group=3, seed=0, tol=2e-4):
+    """convt4 -> batch norm -> convt5 as the decoder chains them: convt4 also accumulates the batch norm's statistics (next_bn) and
+    leaves its bias gradient to the consumer (bias_grad_by_consumer=True), convt5 gets producer_bias=convt4's bias, whose gradient
+    then comes out of vg_bn_bwd_apply_tconv1.  Every parameter has a bound, randomly prefilled .grad; against float64 autograd of
+    the same chain: each gradient must have been added exactly once (the producer's bias gradient too), at the tolerances of
+    run_layer_case."""
+    g = torch.Generator().manual_seed(seed)
+    s4 = ConvSpec('convt', 8, 8, (5, 3, 3), 2, name='convt4'); s5 = ConvSpec('convt', 8, 1, _K3, 1, name='convt5')
+    N = groups * per_group
+    x = torch.randn((N, 8) + tuple(isz), generator=g)
+    vals = [0.2 * torch.randn(8, 8, 5, 3, 3, generator=g), 0.1 * torch.randn(8, generator=g), 0.2 * torch.randn(8, 1, 3, 3, 3, generator=g),
+            0.1 * torch.randn(1, generator=g), 1 + 0.3 * torch.randn(8, generator=g), 0.2 * torch.randn(8, generator=g)]
+    names = ['w4', 'b4', 'w5', 'b5', 'gamma', 'beta']
+    rl = [x.double().requires_grad_(True)] + [v.double().requires_grad_(True) for v in vals]
+    p1 = ref_layer(rl[0], rl[1], rl[2], None, None, s4, True, per_group)
+    y_ref = ref_layer(p1, rl[3], rl[4], rl[5], rl[6], s5, True, per_group)
+    gy = torch.randn(y_ref.shape, generator=g)
+    ref_grads = torch.autograd.grad(y_ref, rl, gy.double())
+    xd = x.to(dev).requires_grad_(True)
+    w4, b4, w5, b5, gamma, beta = params = [torch.nn.Parameter(v.to(dev)) for v in vals]
+    rs = _bind_random_grads(params, g)
+    p1d, st = ops.bn_conv_act(xd, w4, b4, None, None, s4, True, per_group, next_bn=per_group, bias_grad_by_consumer=True)
+    y = ops.bn_conv_act(p1d, w5, b5, gamma, beta, s5, True, per_group, pre_stats=st, producer_bias=b4)
+    np.testing.assert_allclose(y.detach().cpu().numpy(), y_ref.detach().numpy(), rtol=tol, atol=tol, err_msg='chain fwd')
+    got = torch.autograd.grad(y, [xd] + params, gy.to(dev), allow_unused=True)
+    if xd.is_cuda:
+        ops.join_side_stream(xd.device)
+    for t, r, gr, want, nm in zip(params, rs, got[1:], ref_grads[1:], names):
+        assert gr is None, 'chain d%s: autograd was handed a tensor although .grad is bound' % nm
+        want = want.numpy()
+        scale = max(1.0, float(np.abs(want).max()))
+        np.testing.assert_allclose((t.grad.cpu() - r).numpy(), want, rtol=5 * tol, atol=5 * tol * scale, err_msg='chain d' + nm)
+    want = ref_grads[0].numpy()
+    np.testing.assert_allclose(got[0].cpu().numpy(), want, rtol=5 * tol, atol=5 * tol * max(1.0, float(np.abs(want).max())), err_msg='chain dx')
 
 
 def ref_gam(logits, gain, x, eps, glm):
@@ -581,6 +644,605 @@ def conv_mm_coverage(dev=None):
             N = case[7] * case[8]
             assert N * bps > 2048, cid
             cov['loops'] += 1; cov['loops_stats'] += bool(stats)
+    return cov
+
+
+# --------------------------------------------------------------------------- weight gradient (vg_wgrad3d), directly
+WG_SPECS = {
+    'conv1': ConvSpec('conv', 1, 8, _K3, 1),
+    'conv2': ConvSpec('conv', 8, 8, _K3, 2),
+    'conv3': ConvSpec('conv', 8, 16, _K3, 1),
+    'conv4': ConvSpec('conv', 16, 16, _K3, 2),
+    'conv5': ConvSpec('conv', 16, 16, _K3, 1),
+    'convt1': ConvSpec('convt', 16, 16, _K3, 1),
+    'convt2p': ConvSpec('convt', 16, 16, _K3, 2, (1, 0, 1), (1, 0, 1)),      # the padded convt2 of the 41x49x35 network
+    'convt2': ConvSpec('convt', 16, 16, _K3, 2),                             # the plain one of the other two
+    'convt3': ConvSpec('convt', 16, 8, _K3, 1),
+    'convt4': ConvSpec('convt', 8, 8, (5, 3, 3), 2),
+    'convt4hr': ConvSpec('convt', 8, 8, (4, 4, 4), 2),                       # 82x98x70
+    'convt4toy': ConvSpec('convt', 8, 8, _K3, 2),                            # 21x21x21
+    'convt5': ConvSpec('convt', 8, 1, _K3, 1),
+    # no layer of the networks: the PA = 1 instances of the two plane-shift (DSH) families, which the library builds and the planner selects
+    'conv5x3x3': ConvSpec('conv', 8, 8, (5, 3, 3), 2),
+    'conv4x4x4': ConvSpec('conv', 8, 8, (4, 4, 4), 2),
+}
+EPS32 = float(np.finfo(np.float32).eps)
+
+
+def wgrad_tuple(plan):
+    """What names a launch of wgrad_rows_k for the coverage test: (family, PA, UG, RES, GRP, ONE, nbuf class, wave_slabs, loops)."""
+    family = (plan.CA, plan.KD, plan.KH, plan.KW, plan.stride, plan.PAD, plan.DSH)
+    nbuf = 'CA' if plan.nbuf == plan.CA else plan.nbuf
+    return (family, plan.PA, plan.UG, plan.RES, plan.GRP, plan.ONE, nbuf, plan.wave_slabs, int(plan.items > plan.grid))
+
+
+def _wgrad_shapes(spec, isz, N):
+    isz = tuple(isz)
+    return (N, spec.ci) + isz, (N, spec.co) + tuple(spec.out_size(isz))
+
+
+def _check_plan(plan, expect, loop, what):
+    for k, v in (expect or {}).items():
+        have = ('CA' if plan.nbuf == plan.CA else plan.nbuf) if k == 'nbuf' else getattr(plan, k)
+        assert have == v, '%s: plan.%s = %r, the case is there for %r (%r)' % (what, k, have, v, plan)
+    if loop:
+        assert plan.items >= 4097 and plan.items >= 2 * plan.grid and plan.items % plan.grid != 0, (what, plan)
+
+
+def _per_sample(v, groups, per_group, C, dt):
+    """[groups * C] -> [N][C][1][1][1]"""
+    return v.to(dt).view(groups, 1, C, 1, 1, 1).expand(groups, per_group, C, 1, 1, 1).reshape(groups * per_group, C, 1, 1, 1)
+
+
+def run_wgrad_case(dev, spec, isz, groups, per_group, prologue, accumulate, expect, seed=0, loop=False, what=''):
+    """One vg_wgrad3d launch (ops.conv_weight_grad) against the float64 autograd weight gradient of F.conv3d / F.conv_transpose3d
+    applied to the prologue'd input, on the CPU.  `isz` is the LAYER's input size, N = groups * per_group samples.
+    prologue: 'none', 'relu', or 'affine' (ReLU, then a per-(group, channel) scale and shift), applied to x as the forward does --
+    for a conv layer x is the window tensor (PA = 1), for a transposed one the position tensor (PA = 0).
+    accumulate: the output buffer is prefilled with random values r and must hold r + dw afterwards.
+    expect: plan fields the case is there to hit, asserted from ops.wgrad_plan before anything is launched.
+    loop: the case is a persistent-loop case: items >= 4097 > 2 * 2048 >= 2 * grid whatever the occupancy query answers, so every
+    block makes at least two trips, and items is no multiple of the grid.
+
+    Tolerance: tol = max(4 * d32, eps32 * sqrt(K) * max|want|) [+ eps32 * max|r| with accumulate: the one rounding of the final add],
+    d32 = the distance of torch's own fp32 CPU weight gradient to the float64 one on the same inputs, K = N * PD * PH * PW the
+    contraction length (the random-walk rounding floor of an fp32 sum of K terms).  The kernel multiplies in exact fp32 on the matrix
+    cores and sums 4 positions per instruction, per wave, per block and then over the slabs: a pairwise-like order, where torch's
+    CPU kernel is closer to one long chain per sample.
+    Measured err / d32 over WGRAD_CASES, WGRAD_MID_CASES and WGRAD_LOOP_CASES: 0.03 to 1.39 on the host build, 0.06 to 1.40 on the
+    MI355X (the grouped cases 0.05 to 0.45); a launch that lost one item of 4,097 or one wave's share sits at 1e3 to 1e6.
+
+    Returns the record of the case: plan, err, d32, tol."""
+    g = torch.Generator().manual_seed(seed)
+    N = groups * per_group
+    conv = spec.kind == 'conv'
+    xs, ys = _wgrad_shapes(spec, isz, N)
+    relu_in = prologue != 'none'
+    plan = ops.wgrad_plan(spec, xs, ys, relu_in, per_group)
+    _check_plan(plan, expect, loop, what)
+    x = torch.randn(xs, generator=g)
+    dy = torch.randn(ys, generator=g)
+    sc = sh = None
+    if prologue == 'affine':
+        sc = 1 + 0.3 * torch.randn(groups * spec.ci, generator=g); sh = 0.2 * torch.randn(groups * spec.ci, generator=g)
+    wshape = ((spec.co, spec.ci) if conv else (spec.ci, spec.co)) + tuple(spec.k)
+    r = torch.randn(wshape, generator=g) * 3
+
+    def wgrad(dt):
+        h = x.to(dt)
+        if relu_in:
+            h = torch.relu(h)
+        if sc is not None:
+            h = h * _per_sample(sc, groups, per_group, spec.ci, dt) + _per_sample(sh, groups, per_group, spec.ci, dt)
+        w0 = torch.zeros(wshape, dtype=dt, requires_grad=True)
+        y = F.conv3d(h, w0, None, spec.stride) if conv else F.conv_transpose3d(h, w0, None, spec.stride, spec.pad, spec.outpad)
+        return torch.autograd.grad(y, w0, dy.to(dt))[0]
+    want = wgrad(torch.float64)
+    d32 = float((wgrad(torch.float32).double() - want).abs().max())
+    P = ys[2:] if conv else xs[2:]
+    K = N * P[0] * P[1] * P[2]
+    wmax = float(want.abs().max())
+    tol = max(4 * d32, EPS32 * K ** 0.5 * wmax)
+    scd = sc.to(dev) if sc is not None else None; shd = sh.to(dev) if sh is not None else None
+    xd, dyd = x.to(dev), dy.to(dev)
+    rec = dict(plan=plan, d32=d32)
+    for acc in (accumulate if isinstance(accumulate, (tuple, list)) else (accumulate,)):
+        tol_a = tol
+        if acc:
+            out = r.clone().to(dev)
+            assert ops.conv_weight_grad(xd, dyd, spec, relu_in, scd, shd, per_group, out=out) is None
+            want_out = r.double() + want
+            tol_a += EPS32 * float(r.abs().max())
+        else:
+            out = ops.conv_weight_grad(xd, dyd, spec, relu_in, scd, shd, per_group)
+            want_out = want
+        assert tuple(out.shape) == wshape
+        err = float((out.cpu().double() - want_out).abs().max())
+        print('wgrad %s%s isz %r N %d (%d x %d) %s acc %d plan %r: err %.3g d32 %.3g err/d32 %.2f tol %.3g'
+              % (what + ' ' if what else '', spec.kind + 'x'.join(map(str, spec.k)) + '_%d>%d_s%d' % (spec.ci, spec.co, spec.stride), tuple(isz), N,
+                 groups, per_group, prologue, int(bool(acc)), tuple(plan), err, d32, err / max(d32, 1e-30), tol_a))
+        assert err <= tol_a, 'wgrad %s %r accumulate %d: max error %.3g > tol %.3g (d32 %.3g, plan %r)' % (what, tuple(isz), acc, err, tol_a, d32, plan)
+        rec.update(err=max(err, rec.get('err', 0.0)), tol=tol_a)
+    return rec
+
+
+def run_wgrad_grouped_case(dev, C, isz, groups, per_group, relu, expect, sums_after=False, seed=0, loop=False, what=''):
+    """vg_wgrad3d_grouped (ops.wgrad_grouped) for a C -> 1 channel 3x3x3 stride-1 transposed conv with input size `isz`, in_scale /
+    in_shift = rstd / -mean * rstd of relu?(p) per (group, channel), against float64: rows c < C = per-group weight gradients against
+    the normalised activation, row C = the per-tap sums of dy over the positions each tap meets.  Tolerance per group as in
+    run_wgrad_case with K = per_group * D * H * W and d32 from torch's fp32 weight gradient of the same group (the row of sums has
+    the same contraction length; its fp32 reference is F.conv_transpose3d's weight gradient against a tensor of ones).
+    loop: grp_items >= 2 * ipb, every block of a group walks at least two of its items.
+    sums_after: follow with vg_bn_tconv1_sums (ops.bn_tconv1_sums) and check `sums` (float64 from the fp32 q: bound = the
+    propagated tolerance of q, sum_k |w| tol) and dw = gamma * sum_g q[g][c] + beta * sum_g q[g][C] with accumulate 0 and 1."""
+    g = torch.Generator().manual_seed(seed)
+    N = groups * per_group
+    spec = ConvSpec('convt', C, 1, _K3, 1)
+    xs, ys = _wgrad_shapes(spec, isz, N)
+    plan = ops.wgrad_plan(spec, xs, ys, relu, per_group, grouped=True)
+    _check_plan(plan, expect, False, what)
+    if loop:
+        assert plan.grp_items >= 2 * plan.ipb and plan.grp_items % plan.ipb != 0, (what, plan)
+    p = torch.randn(xs, generator=g) + 0.3
+    dy = torch.randn(ys, generator=g)
+    h = torch.relu(p.double()) if relu else p.double()
+    hg = h.reshape(groups, per_group, C, -1)
+    mean = hg.mean((1, 3)); rstd = (hg.var((1, 3), unbiased=False) + ops.BN_EPS).rsqrt()          # [G][C]
+    scale = rstd.float().reshape(-1); shift = (-(mean * rstd)).float().reshape(-1)                # what the model passes (fp32)
+
+    def ref(dt):
+        hh = (torch.relu(p.to(dt)) if relu else p.to(dt)) * _per_sample(scale, groups, per_group, C, dt) + _per_sample(shift, groups, per_group, C, dt)
+        hh = torch.cat([hh, torch.ones((N, 1) + tuple(isz), dtype=dt)], 1)                     # the constant-one position channel
+        rows = []
+        for gi in range(groups):
+            w0 = torch.zeros((C + 1, 1, 3, 3, 3), dtype=dt, requires_grad=True)
+            sl = slice(gi * per_group, (gi + 1) * per_group)
+            rows.append(torch.autograd.grad(F.conv_transpose3d(hh[sl], w0), w0, dy[sl].to(dt))[0].reshape(C + 1, 27))
+        return torch.stack(rows)
+    want = ref(torch.float64)
+    d32 = float((ref(torch.float32).double() - want).abs().max())
+    K = per_group * isz[0] * isz[1] * isz[2]
+    tol = max(4 * d32, EPS32 * K ** 0.5 * float(want.abs().max()))
+    q = ops.wgrad_grouped(dy.to(dev), p.to(dev), scale.to(dev), shift.to(dev), relu, per_group)
+    assert tuple(q.shape) == (groups, C + 1, 27)
+    err = float((q.cpu().double() - want).abs().max())
+    print('wgrad grouped %s C %d isz %r N %d (%d x %d) relu %d plan %r: err %.3g d32 %.3g err/d32 %.2f tol %.3g'
+          % (what, C, tuple(isz), N, groups, per_group, int(relu), tuple(plan), err, d32, err / max(d32, 1e-30), tol))
+    assert err <= tol, 'wgrad grouped %s: max error %.3g > tol %.3g (d32 %.3g, plan %r)' % (what, err, tol, d32, plan)
+    if sums_after:
+        w = 0.2 * torch.randn(C, 1, 3, 3, 3, generator=g); gamma = 1 + 0.3 * torch.randn(C, generator=g); beta = 0.2 * torch.randn(C, generator=g)
+        w2 = w.double().reshape(C, 27)
+        sums_w = torch.stack([(w2[None] * want[:, C:C + 1]).sum(2), (w2[None] * want[:, :C]).sum(2)], 2).reshape(groups * C, 2)
+        dw_w = gamma.double()[:, None] * want[:, :C].sum(0) + beta.double()[:, None] * want[:, C].sum(0)[None]
+        wabs = float(w2.abs().sum(1).max())
+        # dw: |gamma| * G * tol + |beta| * G * tol from q, one fp32 rounding of the result
+        tol_dw = (float(gamma.abs().max()) + float(beta.abs().max())) * groups * tol + EPS32 * float(dw_w.abs().max())
+        for acc in (0, 1):
+            r = 3 * torch.randn(C, 1, 3, 3, 3, generator=g)
+            dw = r.clone().to(dev)
+            sums = ops.bn_tconv1_sums(q, w.to(dev), gamma.to(dev), beta.to(dev), dw, acc)
+            es = float((sums.cpu() - sums_w).abs().max())
+            want_dw = dw_w.reshape(C, 1, 3, 3, 3) + (r.double() if acc else 0)
+            ed = float((dw.cpu().double() - want_dw).abs().max())
+            td = tol_dw + (EPS32 * float(r.abs().max() + dw_w.abs().max()) if acc else 0)
+            print('  bn_tconv1_sums acc %d: sums err %.3g bound %.3g, dw err %.3g bound %.3g' % (acc, es, wabs * tol, ed, td))
+            assert es <= wabs * tol, 'sums: %.3g > %.3g' % (es, wabs * tol)
+            assert ed <= td, 'dw (accumulate %d): %.3g > %.3g' % (acc, ed, td)
+    return dict(plan=plan, err=err, d32=d32, tol=tol)
+
+
+# One item per block (items <= 512 <= grid: every block closes per-wave slabs after its only item): the (family, PA, UG, RES, ONE)
+# instances of wgrad_rows_k and, for CA > 1, the slot schemes (nbuf = CA, 2, 1) that launch_rows selects over the scan of
+# wgrad_selectable(); check_wgrad_coverage repeats that scan and asserts that a listed case runs each combination it finds (155).  Found with ops.wgrad_plan: per instance the cheapest shape of a scan over row widths
+# (every k-step count class), plane heights (tall planes push the best tile out of the all-channels-resident budget) and sample
+# counts (below 512 items the planner prefers small tiles, so the non-resident ONE = 2 / 3 instances need 32 to 128 samples).
+# Each runs with accumulate 0 and 1.  (id, spec, layer input size, groups, per_group, prologue, plan fields asserted)
+WGRAD_CASES = [
+    ('conv1-ug2', 'conv1', (4, 5, 7), 2, 1, 'affine', {'PA': 1, 'UG': 2, 'RES': 0, 'ONE': 0, 'nbuf': 'CA'}),   # tile 1x2, 8 items
+    ('conv1-ug3', 'conv1', (4, 5, 12), 2, 1, 'relu', {'PA': 1, 'UG': 3, 'RES': 0, 'ONE': 0, 'nbuf': 'CA'}),   # tile 1x2, 8 items
+    ('conv1-ug3-one6', 'conv1', (4, 5, 35), 2, 1, 'affine', {'PA': 1, 'UG': 3, 'RES': 0, 'ONE': 6, 'nbuf': 'CA'}),   # tile 1x2, 8 items
+    ('conv1-ug4', 'conv1', (4, 5, 28), 2, 1, 'none', {'PA': 1, 'UG': 4, 'RES': 0, 'ONE': 0, 'nbuf': 'CA'}),   # tile 1x2, 8 items
+    ('conv1-ug4-one2', 'conv1', (4, 5, 16), 2, 1, 'affine', {'PA': 1, 'UG': 4, 'RES': 0, 'ONE': 2, 'nbuf': 'CA'}),   # tile 1x2, 8 items
+    ('conv1-ug4-one3', 'conv1', (4, 5, 18), 2, 1, 'relu', {'PA': 1, 'UG': 4, 'RES': 0, 'ONE': 3, 'nbuf': 'CA'}),   # tile 1x2, 8 items
+    ('conv2-ug2-nbuf2', 'conv2', (5, 9, 77), 2, 1, 'affine', {'PA': 1, 'UG': 2, 'RES': 0, 'ONE': 0, 'nbuf': 2}),   # tile 1x3, 8 items
+    ('conv2-ug2-res', 'conv2', (5, 7, 77), 2, 1, 'none', {'PA': 1, 'UG': 2, 'RES': 1, 'ONE': 0, 'nbuf': 'CA'}),   # tile 1x2, 8 items
+    ('conv2-ug2-res-one2', 'conv2', (5, 7, 11), 2, 1, 'affine', {'PA': 1, 'UG': 2, 'RES': 1, 'ONE': 2, 'nbuf': 'CA'}),   # tile 1x2, 8 items
+    ('conv2-ug2-res-one3', 'conv2', (5, 7, 17), 2, 1, 'relu', {'PA': 1, 'UG': 2, 'RES': 1, 'ONE': 3, 'nbuf': 'CA'}),   # tile 1x2, 8 items
+    ('conv2-ug3-res', 'conv2', (5, 7, 21), 2, 1, 'affine', {'PA': 1, 'UG': 3, 'RES': 1, 'ONE': 0, 'nbuf': 'CA'}),   # tile 1x2, 8 items
+    ('conv2-ug4-nbuf2', 'conv2', (3, 9, 257), 2, 1, 'none', {'PA': 1, 'UG': 4, 'RES': 0, 'ONE': 0, 'nbuf': 2}),   # tile 1x1, 8 items
+    ('conv2-ug4-one2-nbuf2', 'conv2', (17, 43, 29), 4, 8, 'affine', {'PA': 1, 'UG': 4, 'RES': 0, 'ONE': 2, 'nbuf': 2}),   # tile 2x6, 512 items
+    ('conv2-ug4-one3-nbuf2', 'conv2', (17, 25, 33), 4, 8, 'relu', {'PA': 1, 'UG': 4, 'RES': 0, 'ONE': 3, 'nbuf': 2}),   # tile 1x8, 512 items
+    ('conv2-ug4-res', 'conv2', (5, 7, 29), 2, 1, 'affine', {'PA': 1, 'UG': 4, 'RES': 1, 'ONE': 0, 'nbuf': 'CA'}),   # tile 1x2, 8 items
+    ('conv3-ug2-nbuf2', 'conv3', (6, 98, 102), 2, 1, 'none', {'PA': 1, 'UG': 2, 'RES': 0, 'ONE': 0, 'nbuf': 2}),   # tile 3x1, 384 items
+    ('conv3-ug2-res', 'conv3', (4, 5, 40), 2, 1, 'affine', {'PA': 1, 'UG': 2, 'RES': 1, 'ONE': 0, 'nbuf': 'CA'}),   # tile 1x2, 8 items
+    ('conv3-ug2-res-one2', 'conv3', (4, 5, 7), 2, 1, 'relu', {'PA': 1, 'UG': 2, 'RES': 1, 'ONE': 2, 'nbuf': 'CA'}),   # tile 1x2, 8 items
+    ('conv3-ug2-res-one3', 'conv3', (4, 5, 10), 2, 1, 'affine', {'PA': 1, 'UG': 2, 'RES': 1, 'ONE': 3, 'nbuf': 'CA'}),   # tile 1x2, 8 items
+    ('conv3-ug3-res', 'conv3', (4, 5, 12), 2, 1, 'none', {'PA': 1, 'UG': 3, 'RES': 1, 'ONE': 0, 'nbuf': 'CA'}),   # tile 1x2, 8 items
+    ('conv3-ug4-nbuf2', 'conv3', (10, 50, 130), 2, 1, 'affine', {'PA': 1, 'UG': 4, 'RES': 0, 'ONE': 0, 'nbuf': 2}),   # tile 1x2, 384 items
+    ('conv3-ug4-one2-nbuf2', 'conv3', (10, 23, 16), 4, 32, 'relu', {'PA': 1, 'UG': 4, 'RES': 0, 'ONE': 2, 'nbuf': 2}),   # tile 4x11, 512 items
+    ('conv3-ug4-res', 'conv3', (4, 5, 16), 2, 1, 'affine', {'PA': 1, 'UG': 4, 'RES': 1, 'ONE': 0, 'nbuf': 'CA'}),   # tile 1x2, 8 items
+    ('conv4-ug2-nbuf2', 'conv4', (5, 7, 77), 2, 1, 'none', {'PA': 1, 'UG': 2, 'RES': 0, 'ONE': 0, 'nbuf': 2}),   # tile 1x2, 8 items
+    ('conv4-ug2-res', 'conv4', (5, 13, 77), 2, 1, 'affine', {'PA': 1, 'UG': 2, 'RES': 1, 'ONE': 0, 'nbuf': 'CA'}),   # tile 1x1, 24 items
+    ('conv4-ug2-res-one2', 'conv4', (5, 7, 11), 2, 1, 'relu', {'PA': 1, 'UG': 2, 'RES': 1, 'ONE': 2, 'nbuf': 'CA'}),   # tile 1x2, 8 items
+    ('conv4-ug2-res-one3', 'conv4', (5, 7, 17), 2, 1, 'affine', {'PA': 1, 'UG': 2, 'RES': 1, 'ONE': 3, 'nbuf': 'CA'}),   # tile 1x2, 8 items
+    ('conv4-ug3-nbuf2', 'conv4', (5, 9, 37), 2, 1, 'none', {'PA': 1, 'UG': 3, 'RES': 0, 'ONE': 0, 'nbuf': 2}),   # tile 1x3, 8 items
+    ('conv4-ug3-res', 'conv4', (5, 7, 21), 2, 1, 'affine', {'PA': 1, 'UG': 3, 'RES': 1, 'ONE': 0, 'nbuf': 'CA'}),   # tile 1x2, 8 items
+    ('conv4-ug4-nbuf1', 'conv4', (17, 193, 257), 2, 1, 'relu', {'PA': 1, 'UG': 4, 'RES': 0, 'ONE': 0, 'nbuf': 1}),   # tile 1x3, 512 items
+    ('conv4-ug4-nbuf2', 'conv4', (5, 7, 53), 2, 1, 'affine', {'PA': 1, 'UG': 4, 'RES': 0, 'ONE': 0, 'nbuf': 2}),   # tile 1x2, 8 items
+    ('conv4-ug4-one2-nbuf2', 'conv4', (5, 13, 29), 2, 1, 'none', {'PA': 1, 'UG': 4, 'RES': 0, 'ONE': 2, 'nbuf': 2}),   # tile 1x4, 8 items
+    ('conv4-ug4-one3-nbuf2', 'conv4', (7, 7, 33), 2, 1, 'affine', {'PA': 1, 'UG': 4, 'RES': 0, 'ONE': 3, 'nbuf': 2}),   # tile 2x2, 8 items
+    ('conv4-ug4-res', 'conv4', (5, 7, 29), 2, 1, 'relu', {'PA': 1, 'UG': 4, 'RES': 1, 'ONE': 0, 'nbuf': 'CA'}),   # tile 1x2, 8 items
+    ('conv5-ug2-nbuf2', 'conv5', (3, 6, 102), 2, 1, 'affine', {'PA': 1, 'UG': 2, 'RES': 0, 'ONE': 0, 'nbuf': 2}),   # tile 1x1, 8 items
+    ('conv5-ug2-res', 'conv5', (4, 5, 40), 2, 1, 'none', {'PA': 1, 'UG': 2, 'RES': 1, 'ONE': 0, 'nbuf': 'CA'}),   # tile 1x2, 8 items
+    ('conv5-ug2-res-one2', 'conv5', (4, 5, 7), 2, 1, 'affine', {'PA': 1, 'UG': 2, 'RES': 1, 'ONE': 2, 'nbuf': 'CA'}),   # tile 1x2, 8 items
+    ('conv5-ug2-res-one3', 'conv5', (4, 5, 10), 2, 1, 'relu', {'PA': 1, 'UG': 2, 'RES': 1, 'ONE': 3, 'nbuf': 'CA'}),   # tile 1x2, 8 items
+    ('conv5-ug3-res', 'conv5', (4, 5, 12), 2, 1, 'affine', {'PA': 1, 'UG': 3, 'RES': 1, 'ONE': 0, 'nbuf': 'CA'}),   # tile 1x2, 8 items
+    ('conv5-ug4-nbuf2', 'conv5', (3, 6, 130), 2, 1, 'none', {'PA': 1, 'UG': 4, 'RES': 0, 'ONE': 0, 'nbuf': 2}),   # tile 1x1, 8 items
+    ('conv5-ug4-one2-nbuf2', 'conv5', (6, 23, 16), 4, 32, 'affine', {'PA': 1, 'UG': 4, 'RES': 0, 'ONE': 2, 'nbuf': 2}),   # tile 4x6, 512 items
+    ('conv5-ug4-one3-nbuf2', 'conv5', (6, 23, 18), 4, 32, 'relu', {'PA': 1, 'UG': 4, 'RES': 0, 'ONE': 3, 'nbuf': 2}),   # tile 4x6, 512 items
+    ('conv5-ug4-res', 'conv5', (4, 5, 16), 2, 1, 'affine', {'PA': 1, 'UG': 4, 'RES': 1, 'ONE': 0, 'nbuf': 'CA'}),   # tile 1x2, 8 items
+    ('convt1-ug2-nbuf2', 'convt1', (1, 4, 100), 2, 1, 'none', {'PA': 0, 'UG': 2, 'RES': 0, 'ONE': 0, 'nbuf': 2}),   # tile 1x1, 8 items
+    ('convt1-ug2-res', 'convt1', (2, 3, 38), 2, 1, 'affine', {'PA': 0, 'UG': 2, 'RES': 1, 'ONE': 0, 'nbuf': 'CA'}),   # tile 1x2, 8 items
+    ('convt1-ug2-res-one2', 'convt1', (2, 3, 5), 2, 1, 'relu', {'PA': 0, 'UG': 2, 'RES': 1, 'ONE': 2, 'nbuf': 'CA'}),   # tile 1x2, 8 items
+    ('convt1-ug2-res-one3', 'convt1', (2, 3, 8), 2, 1, 'affine', {'PA': 0, 'UG': 2, 'RES': 1, 'ONE': 3, 'nbuf': 'CA'}),   # tile 1x2, 8 items
+    ('convt1-ug3-res', 'convt1', (2, 3, 10), 2, 1, 'none', {'PA': 0, 'UG': 3, 'RES': 1, 'ONE': 0, 'nbuf': 'CA'}),   # tile 1x2, 8 items
+    ('convt1-ug4-nbuf2', 'convt1', (1, 4, 128), 2, 1, 'affine', {'PA': 0, 'UG': 4, 'RES': 0, 'ONE': 0, 'nbuf': 2}),   # tile 1x1, 8 items
+    ('convt1-ug4-one2-nbuf2', 'convt1', (4, 21, 14), 4, 32, 'relu', {'PA': 0, 'UG': 4, 'RES': 0, 'ONE': 2, 'nbuf': 2}),   # tile 4x6, 512 items
+    ('convt1-ug4-one3-nbuf2', 'convt1', (4, 21, 16), 4, 32, 'affine', {'PA': 0, 'UG': 4, 'RES': 0, 'ONE': 3, 'nbuf': 2}),   # tile 4x6, 512 items
+    ('convt1-ug4-res', 'convt1', (2, 3, 14), 2, 1, 'none', {'PA': 0, 'UG': 4, 'RES': 1, 'ONE': 0, 'nbuf': 'CA'}),   # tile 1x2, 8 items
+    ('convt2p-ug2-nbuf2', 'convt2p', (2, 3, 38), 2, 1, 'affine', {'PA': 0, 'UG': 2, 'RES': 0, 'ONE': 0, 'nbuf': 2}),   # tile 1x2, 8 items
+    ('convt2p-ug2-res', 'convt2p', (2, 6, 38), 2, 1, 'relu', {'PA': 0, 'UG': 2, 'RES': 1, 'ONE': 0, 'nbuf': 'CA'}),   # tile 1x1, 24 items
+    ('convt2p-ug2-res-one2', 'convt2p', (2, 3, 5), 2, 1, 'affine', {'PA': 0, 'UG': 2, 'RES': 1, 'ONE': 2, 'nbuf': 'CA'}),   # tile 1x2, 8 items
+    ('convt2p-ug2-res-one3', 'convt2p', (2, 3, 8), 2, 1, 'none', {'PA': 0, 'UG': 2, 'RES': 1, 'ONE': 3, 'nbuf': 'CA'}),   # tile 1x2, 8 items
+    ('convt2p-ug3-nbuf2', 'convt2p', (2, 4, 18), 2, 1, 'affine', {'PA': 0, 'UG': 3, 'RES': 0, 'ONE': 0, 'nbuf': 2}),   # tile 1x3, 8 items
+    ('convt2p-ug3-res', 'convt2p', (2, 3, 10), 2, 1, 'relu', {'PA': 0, 'UG': 3, 'RES': 1, 'ONE': 0, 'nbuf': 'CA'}),   # tile 1x2, 8 items
+    ('convt2p-ug4-nbuf1', 'convt2p', (8, 96, 128), 2, 1, 'affine', {'PA': 0, 'UG': 4, 'RES': 0, 'ONE': 0, 'nbuf': 1}),   # tile 1x3, 512 items
+    ('convt2p-ug4-nbuf2', 'convt2p', (2, 3, 26), 2, 1, 'none', {'PA': 0, 'UG': 4, 'RES': 0, 'ONE': 0, 'nbuf': 2}),   # tile 1x2, 8 items
+    ('convt2p-ug4-one2-nbuf2', 'convt2p', (2, 6, 14), 2, 1, 'affine', {'PA': 0, 'UG': 4, 'RES': 0, 'ONE': 2, 'nbuf': 2}),   # tile 1x4, 8 items
+    ('convt2p-ug4-one3-nbuf2', 'convt2p', (3, 3, 16), 2, 1, 'relu', {'PA': 0, 'UG': 4, 'RES': 0, 'ONE': 3, 'nbuf': 2}),   # tile 2x2, 8 items
+    ('convt2p-ug4-res', 'convt2p', (2, 3, 14), 2, 1, 'affine', {'PA': 0, 'UG': 4, 'RES': 1, 'ONE': 0, 'nbuf': 'CA'}),   # tile 1x2, 8 items
+    ('convt2-ug2-nbuf2', 'convt2', (2, 3, 38), 2, 1, 'none', {'PA': 0, 'UG': 2, 'RES': 0, 'ONE': 0, 'nbuf': 2}),   # tile 1x2, 8 items
+    ('convt2-ug2-res', 'convt2', (2, 6, 38), 2, 1, 'affine', {'PA': 0, 'UG': 2, 'RES': 1, 'ONE': 0, 'nbuf': 'CA'}),   # tile 1x1, 24 items
+    ('convt2-ug2-res-one2', 'convt2', (2, 3, 5), 2, 1, 'relu', {'PA': 0, 'UG': 2, 'RES': 1, 'ONE': 2, 'nbuf': 'CA'}),   # tile 1x2, 8 items
+    ('convt2-ug2-res-one3', 'convt2', (2, 3, 8), 2, 1, 'affine', {'PA': 0, 'UG': 2, 'RES': 1, 'ONE': 3, 'nbuf': 'CA'}),   # tile 1x2, 8 items
+    ('convt2-ug3-nbuf2', 'convt2', (2, 4, 18), 2, 1, 'none', {'PA': 0, 'UG': 3, 'RES': 0, 'ONE': 0, 'nbuf': 2}),   # tile 1x3, 8 items
+    ('convt2-ug3-res', 'convt2', (2, 3, 10), 2, 1, 'affine', {'PA': 0, 'UG': 3, 'RES': 1, 'ONE': 0, 'nbuf': 'CA'}),   # tile 1x2, 8 items
+    ('convt2-ug4-nbuf1', 'convt2', (8, 96, 128), 2, 1, 'relu', {'PA': 0, 'UG': 4, 'RES': 0, 'ONE': 0, 'nbuf': 1}),   # tile 1x3, 512 items
+    ('convt2-ug4-nbuf2', 'convt2', (2, 3, 26), 2, 1, 'affine', {'PA': 0, 'UG': 4, 'RES': 0, 'ONE': 0, 'nbuf': 2}),   # tile 1x2, 8 items
+    ('convt2-ug4-one2-nbuf2', 'convt2', (2, 6, 14), 2, 1, 'none', {'PA': 0, 'UG': 4, 'RES': 0, 'ONE': 2, 'nbuf': 2}),   # tile 1x4, 8 items
+    ('convt2-ug4-one3-nbuf2', 'convt2', (3, 3, 16), 2, 1, 'affine', {'PA': 0, 'UG': 4, 'RES': 0, 'ONE': 3, 'nbuf': 2}),   # tile 2x2, 8 items
+    ('convt2-ug4-res', 'convt2', (2, 3, 14), 2, 1, 'relu', {'PA': 0, 'UG': 4, 'RES': 1, 'ONE': 0, 'nbuf': 'CA'}),   # tile 1x2, 8 items
+    ('convt3-ug2-nbuf2', 'convt3', (4, 96, 100), 2, 1, 'affine', {'PA': 0, 'UG': 2, 'RES': 0, 'ONE': 0, 'nbuf': 2}),   # tile 3x1, 384 items
+    ('convt3-ug2-res', 'convt3', (2, 3, 38), 2, 1, 'none', {'PA': 0, 'UG': 2, 'RES': 1, 'ONE': 0, 'nbuf': 'CA'}),   # tile 1x2, 8 items
+    ('convt3-ug2-res-one2', 'convt3', (2, 3, 5), 2, 1, 'affine', {'PA': 0, 'UG': 2, 'RES': 1, 'ONE': 2, 'nbuf': 'CA'}),   # tile 1x2, 8 items
+    ('convt3-ug2-res-one3', 'convt3', (2, 3, 8), 2, 1, 'relu', {'PA': 0, 'UG': 2, 'RES': 1, 'ONE': 3, 'nbuf': 'CA'}),   # tile 1x2, 8 items
+    ('convt3-ug3-res', 'convt3', (2, 3, 10), 2, 1, 'affine', {'PA': 0, 'UG': 3, 'RES': 1, 'ONE': 0, 'nbuf': 'CA'}),   # tile 1x2, 8 items
+    ('convt3-ug4-nbuf2', 'convt3', (8, 48, 128), 2, 1, 'none', {'PA': 0, 'UG': 4, 'RES': 0, 'ONE': 0, 'nbuf': 2}),   # tile 1x2, 384 items
+    ('convt3-ug4-one2-nbuf2', 'convt3', (8, 21, 14), 4, 32, 'affine', {'PA': 0, 'UG': 4, 'RES': 0, 'ONE': 2, 'nbuf': 2}),   # tile 4x11, 512 items
+    ('convt3-ug4-res', 'convt3', (2, 3, 14), 2, 1, 'relu', {'PA': 0, 'UG': 4, 'RES': 1, 'ONE': 0, 'nbuf': 'CA'}),   # tile 1x2, 8 items
+    ('convt4-ug2-nbuf2', 'convt4', (1, 4, 100), 2, 1, 'affine', {'PA': 0, 'UG': 2, 'RES': 0, 'ONE': 0, 'nbuf': 2}),   # tile 1x1, 16 items
+    ('convt4-ug2-res', 'convt4', (2, 3, 5), 2, 1, 'none', {'PA': 0, 'UG': 2, 'RES': 1, 'ONE': 0, 'nbuf': 'CA'}),   # tile 2x2, 8 items
+    ('convt4-ug3-nbuf2', 'convt4', (3, 4, 36), 2, 1, 'affine', {'PA': 0, 'UG': 3, 'RES': 0, 'ONE': 0, 'nbuf': 2}),   # tile 1x3, 16 items
+    ('convt4-ug3-res', 'convt4', (2, 3, 10), 2, 1, 'relu', {'PA': 0, 'UG': 3, 'RES': 1, 'ONE': 0, 'nbuf': 'CA'}),   # tile 2x2, 8 items
+    ('convt4-ug4-nbuf1', 'convt4', (1, 96, 128), 2, 4, 'affine', {'PA': 0, 'UG': 4, 'RES': 0, 'ONE': 0, 'nbuf': 1}),   # tile 1x3, 512 items
+    ('convt4-ug4-nbuf2', 'convt4', (2, 3, 30), 2, 1, 'none', {'PA': 0, 'UG': 4, 'RES': 0, 'ONE': 0, 'nbuf': 2}),   # tile 2x2, 8 items
+    ('convt4-ug4-one2-nbuf2', 'convt4', (4, 6, 14), 4, 32, 'affine', {'PA': 0, 'UG': 4, 'RES': 0, 'ONE': 2, 'nbuf': 2}),   # tile 3x4, 512 items
+    ('convt4-ug4-one3-nbuf2', 'convt4', (4, 21, 16), 4, 8, 'relu', {'PA': 0, 'UG': 4, 'RES': 0, 'ONE': 3, 'nbuf': 2}),   # tile 1x8, 480 items
+    ('convt4-ug4-res', 'convt4', (2, 3, 14), 2, 1, 'affine', {'PA': 0, 'UG': 4, 'RES': 1, 'ONE': 0, 'nbuf': 'CA'}),   # tile 2x2, 8 items
+    ('convt4hr-ug2-nbuf2', 'convt4hr', (1, 4, 100), 2, 1, 'none', {'PA': 0, 'UG': 2, 'RES': 0, 'ONE': 0, 'nbuf': 2}),   # tile 1x1, 16 items
+    ('convt4hr-ug2-res', 'convt4hr', (2, 3, 5), 2, 1, 'affine', {'PA': 0, 'UG': 2, 'RES': 1, 'ONE': 0, 'nbuf': 'CA'}),   # tile 2x2, 8 items
+    ('convt4hr-ug3-nbuf2', 'convt4hr', (4, 96, 33), 2, 1, 'relu', {'PA': 0, 'UG': 3, 'RES': 0, 'ONE': 0, 'nbuf': 2}),   # tile 4x1, 384 items
+    ('convt4hr-ug3-res', 'convt4hr', (2, 3, 10), 2, 1, 'affine', {'PA': 0, 'UG': 3, 'RES': 1, 'ONE': 0, 'nbuf': 'CA'}),   # tile 2x2, 8 items
+    ('convt4hr-ug4-nbuf1', 'convt4hr', (1, 96, 128), 2, 4, 'none', {'PA': 0, 'UG': 4, 'RES': 0, 'ONE': 0, 'nbuf': 1}),   # tile 1x3, 512 items
+    ('convt4hr-ug4-nbuf2', 'convt4hr', (1, 4, 128), 2, 1, 'affine', {'PA': 0, 'UG': 4, 'RES': 0, 'ONE': 0, 'nbuf': 2}),   # tile 1x1, 16 items
+    ('convt4hr-ug4-one2-nbuf2', 'convt4hr', (4, 6, 14), 4, 32, 'relu', {'PA': 0, 'UG': 4, 'RES': 0, 'ONE': 2, 'nbuf': 2}),   # tile 3x4, 512 items
+    ('convt4hr-ug4-one3-nbuf2', 'convt4hr', (4, 6, 16), 4, 32, 'affine', {'PA': 0, 'UG': 4, 'RES': 0, 'ONE': 3, 'nbuf': 2}),   # tile 3x4, 512 items
+    ('convt4hr-ug4-res', 'convt4hr', (2, 3, 14), 2, 1, 'none', {'PA': 0, 'UG': 4, 'RES': 1, 'ONE': 0, 'nbuf': 'CA'}),   # tile 2x2, 8 items
+    ('convt4toy-ug2-nbuf2', 'convt4toy', (2, 4, 38), 2, 1, 'affine', {'PA': 0, 'UG': 2, 'RES': 0, 'ONE': 0, 'nbuf': 2}),   # tile 1x3, 8 items
+    ('convt4toy-ug2-res', 'convt4toy', (2, 3, 38), 2, 1, 'relu', {'PA': 0, 'UG': 2, 'RES': 1, 'ONE': 0, 'nbuf': 'CA'}),   # tile 1x2, 8 items
+    ('convt4toy-ug2-res-one2', 'convt4toy', (2, 3, 5), 2, 1, 'affine', {'PA': 0, 'UG': 2, 'RES': 1, 'ONE': 2, 'nbuf': 'CA'}),   # tile 1x2, 8 items
+    ('convt4toy-ug2-res-one3', 'convt4toy', (2, 3, 8), 2, 1, 'none', {'PA': 0, 'UG': 2, 'RES': 1, 'ONE': 3, 'nbuf': 'CA'}),   # tile 1x2, 8 items
+    ('convt4toy-ug3-res', 'convt4toy', (2, 3, 10), 2, 1, 'affine', {'PA': 0, 'UG': 3, 'RES': 1, 'ONE': 0, 'nbuf': 'CA'}),   # tile 1x2, 8 items
+    ('convt4toy-ug4-nbuf2', 'convt4toy', (1, 4, 128), 2, 1, 'relu', {'PA': 0, 'UG': 4, 'RES': 0, 'ONE': 0, 'nbuf': 2}),   # tile 1x1, 8 items
+    ('convt4toy-ug4-one2-nbuf2', 'convt4toy', (8, 21, 14), 4, 8, 'affine', {'PA': 0, 'UG': 4, 'RES': 0, 'ONE': 2, 'nbuf': 2}),   # tile 2x6, 512 items
+    ('convt4toy-ug4-one3-nbuf2', 'convt4toy', (8, 12, 16), 4, 8, 'none', {'PA': 0, 'UG': 4, 'RES': 0, 'ONE': 3, 'nbuf': 2}),   # tile 1x8, 512 items
+    ('convt4toy-ug4-res', 'convt4toy', (2, 3, 14), 2, 1, 'affine', {'PA': 0, 'UG': 4, 'RES': 1, 'ONE': 0, 'nbuf': 'CA'}),   # tile 1x2, 8 items
+    ('convt5-ug2', 'convt5', (2, 3, 5), 2, 1, 'relu', {'PA': 0, 'UG': 2, 'RES': 0, 'ONE': 0, 'nbuf': 'CA'}),   # tile 1x2, 8 items
+    ('convt5-ug3', 'convt5', (2, 3, 10), 2, 1, 'affine', {'PA': 0, 'UG': 3, 'RES': 0, 'ONE': 0, 'nbuf': 'CA'}),   # tile 1x2, 8 items
+    ('convt5-ug3-one6', 'convt5', (2, 3, 33), 2, 1, 'none', {'PA': 0, 'UG': 3, 'RES': 0, 'ONE': 6, 'nbuf': 'CA'}),   # tile 1x2, 8 items
+    ('convt5-ug4', 'convt5', (2, 3, 26), 2, 1, 'affine', {'PA': 0, 'UG': 4, 'RES': 0, 'ONE': 0, 'nbuf': 'CA'}),   # tile 1x2, 8 items
+    ('convt5-ug4-one2', 'convt5', (2, 3, 14), 2, 1, 'relu', {'PA': 0, 'UG': 4, 'RES': 0, 'ONE': 2, 'nbuf': 'CA'}),   # tile 1x2, 8 items
+    ('convt5-ug4-one3', 'convt5', (2, 3, 16), 2, 1, 'affine', {'PA': 0, 'UG': 4, 'RES': 0, 'ONE': 3, 'nbuf': 'CA'}),   # tile 1x2, 8 items
+    ('conv5x3x3-ug2-nbuf2', 'conv5x3x3', (5, 9, 201), 2, 1, 'none', {'PA': 1, 'UG': 2, 'RES': 0, 'ONE': 0, 'nbuf': 2}),   # tile 1x1, 16 items
+    ('conv5x3x3-ug2-res', 'conv5x3x3', (7, 7, 11), 2, 1, 'affine', {'PA': 1, 'UG': 2, 'RES': 1, 'ONE': 0, 'nbuf': 'CA'}),   # tile 2x2, 8 items
+    ('conv5x3x3-ug3-nbuf2', 'conv5x3x3', (9, 9, 73), 2, 1, 'relu', {'PA': 1, 'UG': 3, 'RES': 0, 'ONE': 0, 'nbuf': 2}),   # tile 1x3, 16 items
+    ('conv5x3x3-ug3-res', 'conv5x3x3', (7, 7, 21), 2, 1, 'affine', {'PA': 1, 'UG': 3, 'RES': 1, 'ONE': 0, 'nbuf': 'CA'}),   # tile 2x2, 8 items
+    ('conv5x3x3-ug4-nbuf1', 'conv5x3x3', (5, 193, 257), 2, 4, 'none', {'PA': 1, 'UG': 4, 'RES': 0, 'ONE': 0, 'nbuf': 1}),   # tile 1x3, 512 items
+    ('conv5x3x3-ug4-nbuf2', 'conv5x3x3', (7, 7, 61), 2, 1, 'affine', {'PA': 1, 'UG': 4, 'RES': 0, 'ONE': 0, 'nbuf': 2}),   # tile 2x2, 8 items
+    ('conv5x3x3-ug4-one2-nbuf2', 'conv5x3x3', (11, 13, 29), 4, 32, 'relu', {'PA': 1, 'UG': 4, 'RES': 0, 'ONE': 2, 'nbuf': 2}),   # tile 3x4, 512 items
+    ('conv5x3x3-ug4-one3-nbuf2', 'conv5x3x3', (11, 43, 33), 4, 8, 'affine', {'PA': 1, 'UG': 4, 'RES': 0, 'ONE': 3, 'nbuf': 2}),   # tile 1x8, 480 items
+    ('conv5x3x3-ug4-res', 'conv5x3x3', (7, 7, 29), 2, 1, 'none', {'PA': 1, 'UG': 4, 'RES': 1, 'ONE': 0, 'nbuf': 'CA'}),   # tile 2x2, 8 items
+    ('conv4x4x4-ug2-nbuf2', 'conv4x4x4', (4, 10, 202), 2, 1, 'affine', {'PA': 1, 'UG': 2, 'RES': 0, 'ONE': 0, 'nbuf': 2}),   # tile 1x1, 16 items
+    ('conv4x4x4-ug2-res', 'conv4x4x4', (6, 8, 12), 2, 1, 'relu', {'PA': 1, 'UG': 2, 'RES': 1, 'ONE': 0, 'nbuf': 'CA'}),   # tile 2x2, 8 items
+    ('conv4x4x4-ug3-nbuf2', 'conv4x4x4', (10, 194, 68), 2, 1, 'affine', {'PA': 1, 'UG': 3, 'RES': 0, 'ONE': 0, 'nbuf': 2}),   # tile 4x1, 384 items
+    ('conv4x4x4-ug3-res', 'conv4x4x4', (6, 8, 22), 2, 1, 'none', {'PA': 1, 'UG': 3, 'RES': 1, 'ONE': 0, 'nbuf': 'CA'}),   # tile 2x2, 8 items
+    ('conv4x4x4-ug4-nbuf1', 'conv4x4x4', (4, 194, 258), 2, 4, 'affine', {'PA': 1, 'UG': 4, 'RES': 0, 'ONE': 0, 'nbuf': 1}),   # tile 1x3, 512 items
+    ('conv4x4x4-ug4-nbuf2', 'conv4x4x4', (4, 10, 258), 2, 1, 'relu', {'PA': 1, 'UG': 4, 'RES': 0, 'ONE': 0, 'nbuf': 2}),   # tile 1x1, 16 items
+    ('conv4x4x4-ug4-one2-nbuf2', 'conv4x4x4', (10, 14, 30), 4, 32, 'affine', {'PA': 1, 'UG': 4, 'RES': 0, 'ONE': 2, 'nbuf': 2}),   # tile 3x4, 512 items
+    ('conv4x4x4-ug4-one3-nbuf2', 'conv4x4x4', (10, 14, 34), 4, 32, 'none', {'PA': 1, 'UG': 4, 'RES': 0, 'ONE': 3, 'nbuf': 2}),   # tile 3x4, 512 items
+    ('conv4x4x4-ug4-res', 'conv4x4x4', (6, 8, 30), 2, 1, 'affine', {'PA': 1, 'UG': 4, 'RES': 1, 'ONE': 0, 'nbuf': 'CA'}),   # tile 2x2, 8 items
+    # selected only from 512 items on (wide rows of 81 to 212 positions at 128 samples, or rows so wide that one item already fills the tile)
+    ('conv3-ug3-nbuf2', 'conv3', (6, 23, 83), 2, 4, 'affine', {'PA': 1, 'UG': 3, 'RES': 0, 'ONE': 0, 'nbuf': 2}),
+    ('conv3-ug4-one3-nbuf2', 'conv3', (8, 25, 18), 4, 32, 'relu', {'PA': 1, 'UG': 4, 'RES': 0, 'ONE': 3, 'nbuf': 2}),
+    ('conv4-ug2-nbuf1', 'conv4', (5, 13, 205), 4, 32, 'affine', {'PA': 1, 'UG': 2, 'RES': 0, 'ONE': 0, 'nbuf': 1}),
+    ('conv4-ug3-nbuf1', 'conv4', (5, 13, 211), 4, 32, 'none', {'PA': 1, 'UG': 3, 'RES': 0, 'ONE': 0, 'nbuf': 1}),
+    ('conv5-ug3-nbuf2', 'conv5', (3, 3, 83), 2, 1, 'affine', {'PA': 1, 'UG': 3, 'RES': 0, 'ONE': 0, 'nbuf': 2}),
+    ('convt1-ug3-nbuf2', 'convt1', (1, 1, 81), 2, 1, 'affine', {'PA': 0, 'UG': 3, 'RES': 0, 'ONE': 0, 'nbuf': 2}),
+    ('convt2p-ug2-nbuf1', 'convt2p', (2, 6, 102), 4, 32, 'affine', {'PA': 0, 'UG': 2, 'RES': 0, 'ONE': 0, 'nbuf': 1}),
+    ('convt2p-ug3-nbuf1', 'convt2p', (2, 6, 105), 4, 32, 'relu', {'PA': 0, 'UG': 3, 'RES': 0, 'ONE': 0, 'nbuf': 1}),
+    ('convt2-ug2-nbuf1', 'convt2', (2, 6, 102), 4, 32, 'none', {'PA': 0, 'UG': 2, 'RES': 0, 'ONE': 0, 'nbuf': 1}),
+    ('convt2-ug3-nbuf1', 'convt2', (2, 6, 105), 4, 32, 'affine', {'PA': 0, 'UG': 3, 'RES': 0, 'ONE': 0, 'nbuf': 1}),
+    ('convt3-ug3-nbuf2', 'convt3', (4, 21, 81), 2, 4, 'affine', {'PA': 0, 'UG': 3, 'RES': 0, 'ONE': 0, 'nbuf': 2}),
+    ('convt3-ug4-one3-nbuf2', 'convt3', (6, 23, 16), 4, 32, 'affine', {'PA': 0, 'UG': 4, 'RES': 0, 'ONE': 3, 'nbuf': 2}),
+    ('convt4-ug2-nbuf1', 'convt4', (3, 4, 97), 4, 32, 'relu', {'PA': 0, 'UG': 2, 'RES': 0, 'ONE': 0, 'nbuf': 1}),
+    ('convt4-ug3-nbuf1', 'convt4', (2, 3, 105), 4, 32, 'affine', {'PA': 0, 'UG': 3, 'RES': 0, 'ONE': 0, 'nbuf': 1}),
+    ('convt4hr-ug2-nbuf1', 'convt4hr', (3, 4, 97), 4, 32, 'affine', {'PA': 0, 'UG': 2, 'RES': 0, 'ONE': 0, 'nbuf': 1}),
+    ('convt4hr-ug3-nbuf1', 'convt4hr', (3, 4, 105), 4, 32, 'none', {'PA': 0, 'UG': 3, 'RES': 0, 'ONE': 0, 'nbuf': 1}),
+    ('convt4toy-ug3-nbuf2', 'convt4toy', (1, 1, 105), 2, 1, 'affine', {'PA': 0, 'UG': 3, 'RES': 0, 'ONE': 0, 'nbuf': 2}),
+    ('conv5x3x3-ug2-nbuf1', 'conv5x3x3', (9, 9, 195), 4, 32, 'affine', {'PA': 1, 'UG': 2, 'RES': 0, 'ONE': 0, 'nbuf': 1}),
+    ('conv5x3x3-ug3-nbuf1', 'conv5x3x3', (7, 7, 211), 4, 32, 'relu', {'PA': 1, 'UG': 3, 'RES': 0, 'ONE': 0, 'nbuf': 1}),
+    ('conv4x4x4-ug2-nbuf1', 'conv4x4x4', (8, 10, 196), 4, 32, 'affine', {'PA': 1, 'UG': 2, 'RES': 0, 'ONE': 0, 'nbuf': 1}),
+    ('conv4x4x4-ug3-nbuf1', 'conv4x4x4', (8, 10, 212), 4, 32, 'none', {'PA': 1, 'UG': 3, 'RES': 0, 'ONE': 0, 'nbuf': 1}),
+]
+
+# 513 to 640 items with the tile a layer of the networks gets (named behind each case): one item per block where the occupancy query
+# lets the grid grow past 512 blocks -- the cross-wave LDS reduction and one slab per block without the loop -- and a second trip
+# for the first blocks where it stops at 512.  Same fields as WGRAD_CASES; run with accumulate 0 and 1.
+WGRAD_MID_CASES = [
+    ('conv2-mid-w16-3x43-pd-ph', 'conv2', (15, 23, 33), 3, 43, 'affine', {'PA': 1, 'UG': 4, 'RES': 0, 'ONE': 3, 'nbuf': 2, 'TPD': 4, 'TPH': 6, 'items': 516}),   # 41x49x35 conv2
+    ('conv3-mid-w14-2x43-pd-ph', 'conv3', (7, 23, 16), 2, 43, 'affine', {'PA': 1, 'UG': 4, 'RES': 1, 'ONE': 0, 'nbuf': 'CA', 'TPD': 3, 'TPH': 8, 'items': 516}),   # 41x49x35 conv3
+    ('convt2p-mid-w7-3x43-pd-ph', 'convt2p', (5, 3, 7), 3, 43, 'affine', {'PA': 0, 'UG': 2, 'RES': 1, 'ONE': 2, 'nbuf': 'CA', 'TPD': 4, 'TPH': 2, 'items': 516}),   # 41x49x35 convt2
+    ('convt3-mid-w14-3x43-pd-ph', 'convt3', (7, 21, 14), 3, 43, 'affine', {'PA': 0, 'UG': 4, 'RES': 0, 'ONE': 2, 'nbuf': 2, 'TPD': 4, 'TPH': 11, 'items': 516}),   # 41x49x35 convt3
+    ('conv3-mid-w14-3x19-pd', 'conv3', (19, 23, 16), 3, 19, 'affine', {'PA': 1, 'UG': 4, 'RES': 0, 'ONE': 2, 'nbuf': 2, 'TPD': 2, 'TPH': 21, 'items': 513}),   # 41x49x35 conv3
+    ('conv4-mid-w6-3x43-pd-ph', 'conv4', (11, 7, 13), 3, 43, 'affine', {'PA': 1, 'UG': 2, 'RES': 1, 'ONE': 2, 'nbuf': 'CA', 'TPD': 4, 'TPH': 2, 'items': 516}),   # 41x49x35 conv4
+    ('convt1-mid-w5-2x129-pd', 'convt1', (5, 8, 5), 2, 129, 'affine', {'PA': 0, 'UG': 2, 'RES': 1, 'ONE': 2, 'nbuf': 'CA', 'TPD': 3, 'TPH': 8, 'items': 516}),   # 41x49x35 convt1
+    ('conv4-mid-w15-2x43-pd-ph', 'conv4', (11, 45, 31), 2, 43, 'affine', {'PA': 1, 'UG': 4, 'RES': 0, 'ONE': 2, 'nbuf': 2, 'TPD': 3, 'TPH': 8, 'items': 516}),   # 82x98x70 conv4
+    ('conv1-mid-w19-3x43-pd-ph', 'conv1', (9, 11, 21), 3, 43, 'affine', {'PA': 1, 'UG': 3, 'RES': 0, 'ONE': 0, 'nbuf': 'CA', 'TPD': 4, 'TPH': 5, 'items': 516}),   # 21x21x21 conv1
+    ('convt1-mid-w1-3x171', 'convt1', (1, 1, 1), 3, 171, 'affine', {'PA': 0, 'UG': 2, 'RES': 1, 'ONE': 2, 'nbuf': 'CA', 'TPD': 1, 'TPH': 1, 'items': 513}),   # 21x21x21 convt1
+    ('convt4toy-mid-w9-3x43-pd-ph', 'convt4toy', (5, 9, 9), 3, 43, 'affine', {'PA': 0, 'UG': 3, 'RES': 1, 'ONE': 0, 'nbuf': 'CA', 'TPD': 3, 'TPH': 5, 'items': 516}),   # 21x21x21 convt4
+    ('convt5-mid-w19-3x43-pd-ph', 'convt5', (7, 19, 19), 3, 43, 'affine', {'PA': 0, 'UG': 3, 'RES': 0, 'ONE': 0, 'nbuf': 'CA', 'TPD': 4, 'TPH': 10, 'items': 516}),   # 21x21x21 convt5
+    ('conv1-mid-w19-3x43-pd-ph-t4x10', 'conv1', (9, 21, 21), 3, 43, 'affine', {'PA': 1, 'UG': 3, 'RES': 0, 'ONE': 0, 'nbuf': 'CA', 'TPD': 4, 'TPH': 10, 'items': 516}),   # 21x21x21 conv1
+    ('conv2-mid-w9-3x43-pd-ph', 'conv2', (11, 11, 19), 3, 43, 'affine', {'PA': 1, 'UG': 3, 'RES': 1, 'ONE': 0, 'nbuf': 'CA', 'TPD': 3, 'TPH': 4, 'items': 516}),   # 21x21x21 conv2
+    ('convt2-mid-w3-3x171', 'convt2', (3, 3, 3), 3, 171, 'affine', {'PA': 0, 'UG': 2, 'RES': 1, 'ONE': 2, 'nbuf': 'CA', 'TPD': 3, 'TPH': 3, 'items': 513}),   # 21x21x21 convt2
+    ('convt3-mid-w7-2x129-pd', 'convt3', (7, 7, 7), 2, 129, 'affine', {'PA': 0, 'UG': 2, 'RES': 1, 'ONE': 2, 'nbuf': 'CA', 'TPD': 4, 'TPH': 7, 'items': 516}),   # 21x21x21 convt3
+]
+
+# The persistent item loop: items >= 4097 > 2 * 2048 >= 2 * grid whatever the occupancy query answers, and no multiple of 256, so of no
+# grid.  Built by the rule: keep the row width PW of the production layer named behind the case (it alone decides UG and ONE), shrink
+# depth and height as far as (instance, slot scheme, TPD, TPH) stay what production gets -- the same tile gives the same LDS size, so
+# the occupancy query answers as in production and `grid` / `wave_slabs` follow it on either library -- then raise N.  -pd / -ph: the
+# last tile in depth / in rows is partial (a short tile followed by a full one in the same block's LDS).  Groups: 3 x 683, 5 x 205 and
+# 3 x 1366 samples against a stride of grid / items-per-sample samples: a block's successive items cross batch-norm groups;
+# conv3-loop-w14-2x228-pd has 18 items per sample, a stride of at most 2048 / 18 = 113 < 228 samples: they also stay inside one.
+# -small-tile: at the production tile the window tensor of 4,097 items passes 256 MB (16 or 8 channels at stride 2: 100 to 240 KB per item),
+# so depth and height are shrunk further and the planner picks a smaller tile of the same instance and slot scheme; with less LDS the
+# occupancy query may answer more blocks than in production (see WGRAD_NOT_COVERED).  convt4hr-loop-w33 keeps the production tile of
+# the 4x4x4 plane-shift layer with a dy tensor of 428 MB, above the 256 MB limit: a scan of depths and heights on the host build finds no
+# shape with the production tuple (1 x 12 tile, 2 blocks per CU) under about 321 MB at 4,097 items (about 100 KB of dy per item: four window
+# planes of 8 channels per position plane), and a smaller tile changes the occupancy answer and with it `wave_slabs`.
+# (id, spec, layer input size, groups, per_group, prologue, accumulate, plan fields asserted)
+WGRAD_LOOP_CASES = [
+    # the smallest tiles the one-channel family takes at 19-position rows (one item per sample): what the host build can walk in under 20 s
+    ('convt5-loop-w19-7x586-host', 'convt5', (2, 3, 19), 7, 586, 'affine', 1, {'PA': 0, 'UG': 3, 'RES': 0, 'ONE': 0, 'nbuf': 'CA', 'items': 4102}),
+    ('conv1-loop-w19-7x586-host', 'conv1', (4, 5, 21), 7, 586, 'affine', 0, {'PA': 1, 'UG': 3, 'RES': 0, 'ONE': 0, 'nbuf': 'CA', 'items': 4102}),
+    ('conv1-loop-w33-3x683-pd', 'conv1', (7, 14, 35), 3, 683, 'affine', 0, {'PA': 1, 'UG': 3, 'RES': 0, 'ONE': 6, 'nbuf': 'CA', 'TPD': 3, 'TPH': 12, 'items': 4098}),   # 41x49x35 conv1
+    ('conv2-loop-w16-5x410-small-tile', 'conv2', (11, 7, 33), 5, 410, 'affine', 1, {'PA': 1, 'UG': 4, 'RES': 0, 'ONE': 3, 'nbuf': 2, 'TPD': 4, 'TPH': 3, 'items': 4100}),   # 41x49x35 conv2
+    ('conv3-loop-w14-3x683-pd', 'conv3', (7, 10, 16), 3, 683, 'affine', 0, {'PA': 1, 'UG': 4, 'RES': 1, 'ONE': 0, 'nbuf': 'CA', 'TPD': 3, 'TPH': 8, 'items': 4098}),   # 41x49x35 conv3
+    ('convt2p-loop-w7-3x683-pd', 'convt2p', (5, 2, 7), 3, 683, 'affine', 1, {'PA': 0, 'UG': 2, 'RES': 1, 'ONE': 2, 'nbuf': 'CA', 'TPD': 4, 'TPH': 2, 'items': 4098}),   # 41x49x35 convt2
+    ('convt3-loop-w14-5x205-pd-ph', 'convt3', (7, 21, 14), 5, 205, 'affine', 0, {'PA': 0, 'UG': 4, 'RES': 0, 'ONE': 2, 'nbuf': 2, 'TPD': 4, 'TPH': 11, 'items': 4100}),   # 41x49x35 convt3
+    ('convt4-loop-w16-5x410-small-tile', 'convt4', (2, 7, 16), 5, 410, 'affine', 1, {'PA': 0, 'UG': 4, 'RES': 0, 'ONE': 3, 'nbuf': 2, 'TPD': 2, 'TPH': 7, 'items': 4100}),   # 41x49x35 convt4
+    ('convt5-loop-w33-3x683-ph', 'convt5', (3, 23, 33), 3, 683, 'affine', 0, {'PA': 0, 'UG': 3, 'RES': 0, 'ONE': 6, 'nbuf': 'CA', 'TPD': 3, 'TPH': 12, 'items': 4098}),   # 41x49x35 convt5
+    ('conv3-loop-w14-2x228-pd', 'conv3', (19, 23, 16), 2, 228, 'affine', 1, {'PA': 1, 'UG': 4, 'RES': 0, 'ONE': 2, 'nbuf': 2, 'TPD': 2, 'TPH': 21, 'items': 4104}),   # 41x49x35 conv3
+    ('conv4-loop-w6-3x683-pd', 'conv4', (11, 5, 13), 3, 683, 'affine', 0, {'PA': 1, 'UG': 2, 'RES': 1, 'ONE': 2, 'nbuf': 'CA', 'TPD': 4, 'TPH': 2, 'items': 4098}),   # 41x49x35 conv4
+    ('convt1-loop-w5-3x683-pd', 'convt1', (5, 8, 5), 3, 683, 'affine', 1, {'PA': 0, 'UG': 2, 'RES': 1, 'ONE': 2, 'nbuf': 'CA', 'TPD': 3, 'TPH': 8, 'items': 4098}),   # 41x49x35 convt1
+    ('conv1-loop-w68-5x205-pd-ph', 'conv1', (9, 9, 70), 5, 205, 'affine', 0, {'PA': 1, 'UG': 3, 'RES': 0, 'ONE': 0, 'nbuf': 'CA', 'TPD': 4, 'TPH': 4, 'items': 4100}),   # 82x98x70 conv1
+    ('conv2-loop-w33-5x410-small-tile', 'conv2', (11, 3, 67), 5, 410, 'affine', 1, {'PA': 1, 'UG': 3, 'RES': 0, 'ONE': 0, 'nbuf': 2, 'TPD': 4, 'TPH': 1, 'items': 4100}),   # 82x98x70 conv2
+    ('conv3-loop-w31-5x205-pd-ph', 'conv3', (9, 11, 33), 5, 205, 'affine', 0, {'PA': 1, 'UG': 4, 'RES': 0, 'ONE': 0, 'nbuf': 2, 'TPD': 4, 'TPH': 5, 'items': 4100}),   # 82x98x70 conv3
+    ('conv4-loop-w15-5x410-small-tile', 'conv4', (11, 5, 31), 5, 410, 'affine', 1, {'PA': 1, 'UG': 4, 'RES': 0, 'ONE': 2, 'nbuf': 2, 'TPD': 4, 'TPH': 2, 'items': 4100}),   # 82x98x70 conv4
+    ('convt1-loop-w13-5x205-pd-ph', 'convt1', (7, 19, 13), 5, 205, 'affine', 0, {'PA': 0, 'UG': 4, 'RES': 0, 'ONE': 2, 'nbuf': 2, 'TPD': 4, 'TPH': 10, 'items': 4100}),   # 82x98x70 convt1
+    ('convt2-loop-w15-5x410-small-tile', 'convt2', (5, 2, 15), 5, 410, 'affine', 1, {'PA': 0, 'UG': 4, 'RES': 0, 'ONE': 2, 'nbuf': 2, 'TPD': 4, 'TPH': 2, 'items': 4100}),   # 82x98x70 convt2
+    ('convt3-loop-w31-5x205-pd-ph', 'convt3', (7, 9, 31), 5, 205, 'affine', 0, {'PA': 0, 'UG': 4, 'RES': 0, 'ONE': 0, 'nbuf': 2, 'TPD': 4, 'TPH': 5, 'items': 4100}),   # 82x98x70 convt3
+    ('convt4hr-loop-w33-5x205-ph', 'convt4hr', (1, 23, 33), 5, 205, 'affine', 1, {'PA': 0, 'UG': 3, 'RES': 0, 'ONE': 0, 'nbuf': 2, 'TPD': 1, 'TPH': 12, 'items': 4100}),   # 82x98x70 convt4
+    ('convt5-loop-w68-5x205-pd-ph', 'convt5', (7, 7, 68), 5, 205, 'affine', 0, {'PA': 0, 'UG': 3, 'RES': 0, 'ONE': 0, 'nbuf': 'CA', 'TPD': 4, 'TPH': 4, 'items': 4100}),   # 82x98x70 convt5
+    ('conv1-loop-w19-3x683-pd', 'conv1', (9, 7, 21), 3, 683, 'affine', 1, {'PA': 1, 'UG': 3, 'RES': 0, 'ONE': 0, 'nbuf': 'CA', 'TPD': 4, 'TPH': 5, 'items': 4098}),   # 21x21x21 conv1
+    ('convt1-loop-w1-3x1366', 'convt1', (1, 1, 1), 3, 1366, 'affine', 0, {'PA': 0, 'UG': 2, 'RES': 1, 'ONE': 2, 'nbuf': 'CA', 'TPD': 1, 'TPH': 1, 'items': 4098}),   # 21x21x21 convt1
+    ('convt4toy-loop-w9-5x205-pd-ph', 'convt4toy', (5, 9, 9), 5, 205, 'affine', 1, {'PA': 0, 'UG': 3, 'RES': 1, 'ONE': 0, 'nbuf': 'CA', 'TPD': 3, 'TPH': 5, 'items': 4100}),   # 21x21x21 convt4
+    ('convt5-loop-w19-5x205-pd-ph', 'convt5', (7, 19, 19), 5, 205, 'affine', 0, {'PA': 0, 'UG': 3, 'RES': 0, 'ONE': 0, 'nbuf': 'CA', 'TPD': 4, 'TPH': 10, 'items': 4100}),   # 21x21x21 convt5
+    ('conv1-loop-w19-5x205-pd-ph', 'conv1', (9, 21, 21), 5, 205, 'affine', 1, {'PA': 1, 'UG': 3, 'RES': 0, 'ONE': 0, 'nbuf': 'CA', 'TPD': 4, 'TPH': 10, 'items': 4100}),   # 21x21x21 conv1
+    ('conv2-loop-w9-3x683-pd', 'conv2', (11, 9, 19), 3, 683, 'affine', 0, {'PA': 1, 'UG': 3, 'RES': 1, 'ONE': 0, 'nbuf': 'CA', 'TPD': 3, 'TPH': 4, 'items': 4098}),   # 21x21x21 conv2
+    ('convt2-loop-w3-3x1366', 'convt2', (3, 3, 3), 3, 1366, 'affine', 1, {'PA': 0, 'UG': 2, 'RES': 1, 'ONE': 2, 'nbuf': 'CA', 'TPD': 3, 'TPH': 3, 'items': 4098}),   # 21x21x21 convt2
+    ('convt3-loop-w7-3x683-pd', 'convt3', (7, 7, 7), 3, 683, 'affine', 0, {'PA': 0, 'UG': 2, 'RES': 1, 'ONE': 2, 'nbuf': 'CA', 'TPD': 4, 'TPH': 7, 'items': 4098}),   # 21x21x21 convt3
+]
+
+# (id, C, input size, groups, per_group, relu, plan fields asserted, follow with vg_bn_tconv1_sums, loop)
+WGRAD_GROUPED_CASES = [
+    ('grouped-small-w33', 8, (3, 4, 33), 2, 2, True, {'GRP': 1, 'ONE': 6, 'wave_slabs': 1}, False, False),          # ipb == grp_items, per-wave slabs
+    ('grouped-mid-w19', 8, (2, 3, 19), 2, 300, True, {'GRP': 1, 'ONE': 0, 'items': 600}, True, False),               # ipb == grp_items where the grid may pass 512
+    ('grouped-loop-w33-3x1366', 8, (2, 3, 33), 3, 1366, True, {'GRP': 1, 'ONE': 6, 'items': 4098}, False, True),     # odd number of groups; ipb <= 682 < grp_items / 2
+    ('grouped-loop-w19-2x2051', 8, (2, 3, 19), 2, 2051, False, {'GRP': 1, 'ONE': 0, 'items': 4102}, True, True),     # ipb <= 1024 < grp_items / 2; then vg_bn_tconv1_sums
+]
+
+# On the host build a case costs what its items cost: these measured 20 to 52 s (the others 0.1 to 17 s), above the 20 s a host case
+# may take, so they run on the GPU only (milliseconds there) -- the single-slot (nbuf = 1) cases with their 128-position rows and the
+# non-resident compile-time-row instances that need 128 samples
+WGRAD_GPU_ONLY = ('conv3-ug2-nbuf2', 'conv3-ug4-nbuf2', 'conv3-ug4-one2-nbuf2', 'conv4-ug4-nbuf1', 'conv5-ug4-one2-nbuf2', 'conv5-ug4-one3-nbuf2',
+                  'convt1-ug4-one2-nbuf2', 'convt1-ug4-one3-nbuf2', 'convt2p-ug4-nbuf1', 'convt2-ug4-nbuf1', 'convt3-ug4-one2-nbuf2',
+                  'convt4-ug4-nbuf1', 'convt4hr-ug4-nbuf1', 'conv5x3x3-ug4-nbuf1', 'conv4x4x4-ug4-nbuf1',
+                  # mid cases on the large production tiles: 31 to 68 s
+                  'conv2-mid-w16-3x43-pd-ph', 'conv3-mid-w14-2x43-pd-ph', 'convt3-mid-w14-3x43-pd-ph', 'conv3-mid-w14-3x19-pd',
+                  'convt1-mid-w5-2x129-pd', 'conv4-mid-w15-2x43-pd-ph',
+                  # selected only from 512 items on: 336 items on 81 / 83-position rows 27 and 23 s; the sixteen 128-sample cases (512 items on
+                  # rows of 16 to 212 positions) were not timed one by one: a host run of them was cut off after 15 minutes
+                  'conv3-ug3-nbuf2', 'convt3-ug3-nbuf2', 'conv3-ug4-one3-nbuf2', 'convt3-ug4-one3-nbuf2', 'conv4-ug2-nbuf1', 'conv4-ug3-nbuf1',
+                  'convt2p-ug2-nbuf1', 'convt2p-ug3-nbuf1', 'convt2-ug2-nbuf1', 'convt2-ug3-nbuf1', 'convt4-ug2-nbuf1', 'convt4-ug3-nbuf1',
+                  'convt4hr-ug2-nbuf1', 'convt4hr-ug3-nbuf1', 'conv5x3x3-ug2-nbuf1', 'conv5x3x3-ug3-nbuf1', 'conv4x4x4-ug2-nbuf1',
+                  'conv4x4x4-ug3-nbuf1')
+
+# Loop cases: a host item costs 3 to 6 ms, so 4,097 items take 11 s (these two: 11.7 and 10.7 s) on the smallest tiles and 23 to 70 s
+# on the production tiles (convt1-loop-w1 25 s, conv1-loop-w19-3x683 24 s, conv4-loop-w6 41 s, convt2p-loop-w7 40 s, conv1-loop-w33 51 s,
+# convt2-loop-w3 70 s; the larger ones were not waited for): every other plain loop case runs on the GPU only.  The grouped loop cases
+# take 13 and 16 s and run on the host build.
+WGRAD_LOOP_HOST = ('convt5-loop-w19-7x586-host', 'conv1-loop-w19-7x586-host')
+WGRAD_LOOP_GPU_ONLY = tuple(c[0] for c in WGRAD_LOOP_CASES if c[0] not in WGRAD_LOOP_HOST)
+
+
+def run_wgrad_instance_listed(dev, case, seed=0):
+    """a case of WGRAD_CASES / WGRAD_MID_CASES: written and accumulated, one float64 reference"""
+    cid, sname, isz, groups, per_group, prologue, expect = case
+    return run_wgrad_case(dev, WG_SPECS[sname], isz, groups, per_group, prologue, (0, 1), expect, seed, what=cid)
+
+
+def run_wgrad_loop_listed(dev, case, seed=0):
+    cid, sname, isz, groups, per_group, prologue, acc, expect = case
+    return run_wgrad_case(dev, WG_SPECS[sname], isz, groups, per_group, prologue, acc, expect, seed, loop=True, what=cid)
+
+
+def run_wgrad_grouped_listed(dev, case, seed=0):
+    cid, C, isz, groups, per_group, relu, expect, sums_after, loop = case
+    return run_wgrad_grouped_case(dev, C, isz, groups, per_group, relu, expect, sums_after, seed, loop, what=cid)
+
+
+# layers of LAYERS that test_layer_bound_gradients runs: name -> (index, with batch norm)
+BOUND_LAYERS = {'conv3': (2, True), 'conv2': (1, False), 'convt2': (6, False), 'convt4': (8, False), 'convt5': (9, True)}
+
+
+# the bench configurations: (image, ((batch B, covariates C), ...)); encoder launches see N = B samples, decoder launches N = B * (C + 1).
+# 82x98x70: the per-GPU slice of `bench.py --hires` (batch 64, 12 covariates).
+WGRAD_NETS = (((41, 49, 35), ((32, 3), (64, 8))), ((82, 98, 70), ((64, 12),)), ((21, 21, 21), ((32, 3), (64, 8))))
+
+
+def wgrad_production_plans():
+    """-> [(image, B, C, layer, plan)] for every weight-gradient launch of the three networks at the bench sample counts, plus the grouped
+    launch of the last decoder stage ('convt5/grouped'), from the library's planner (nothing is launched)."""
+    from vae_gam_amd.schema import net_geometry
+    out = []
+    for img, cfgs in WGRAD_NETS:
+        geo = net_geometry(img)
+        for B, C in cfgs:
+            for specs, sizes, N in ((geo.enc, geo.enc_sizes(), B), (geo.dec, geo.dec_sizes(), B * (C + 1))):
+                for spec, isz in zip(specs, sizes):
+                    out.append((img, B, C, spec.name, ops.wgrad_plan(spec, *_wgrad_shapes(spec, isz, N), True, B)))
+            spec, isz = geo.dec[-1], geo.dec_sizes()[-2]
+            out.append((img, B, C, spec.name + '/grouped', ops.wgrad_plan(spec, *_wgrad_shapes(spec, isz, B * (C + 1)), True, B, grouped=True)))
+    return out
+
+
+def wgrad_case_plans():
+    """-> [(id, plan, accumulate values, loop, grouped, position size)] of every listed case"""
+    out = []
+    for cid, sname, isz, groups, per_group, prologue, expect in WGRAD_CASES + WGRAD_MID_CASES:
+        spec = WG_SPECS[sname]; xs, ys = _wgrad_shapes(spec, isz, groups * per_group)
+        out.append((cid, ops.wgrad_plan(spec, xs, ys, prologue != 'none', per_group), {0, 1}, False, False, (ys if spec.kind == 'conv' else xs)[2:]))
+    for cid, sname, isz, groups, per_group, prologue, acc, expect in WGRAD_LOOP_CASES:
+        spec = WG_SPECS[sname]; xs, ys = _wgrad_shapes(spec, isz, groups * per_group)
+        out.append((cid, ops.wgrad_plan(spec, xs, ys, prologue != 'none', per_group), {acc}, True, False, (ys if spec.kind == 'conv' else xs)[2:]))
+    for cid, C, isz, groups, per_group, relu, expect, sums_after, loop in WGRAD_GROUPED_CASES:
+        spec = ConvSpec('convt', C, 1, _K3, 1); xs, ys = _wgrad_shapes(spec, isz, groups * per_group)
+        out.append((cid, ops.wgrad_plan(spec, xs, ys, relu, per_group, grouped=True), {0, 1} if sums_after else {0}, loop, True, xs[2:]))
+    return out
+
+
+_SCAN_PLANES = ((1, 1), (2, 3), (2, 6), (3, 4), (4, 6), (4, 8), (6, 23), (8, 21), (10, 50), (4, 96), (8, 96), (2, 8), (4, 21), (8, 12))
+
+
+def wgrad_selectable():
+    """Every (family, PA, UG, RES, GRP = 0, ONE, nbuf class) the planner selects over a scan of what ops can describe: the WG_SPECS
+    layers, rows of 1 to 130 positions, 14 plane sizes (depth x height of the position tensor) and 2, 8, 32 and 128 samples (the last
+    reach the 512 items from which the planner stops preferring small tiles); launches nothing, about 2 s.  -> {combination: example}"""
+    found = {}
+    for sname, spec in WG_SPECS.items():
+        for W in range(1, 131):
+            for D, H in _SCAN_PLANES:
+                P = (D, H, W)
+                isz = tuple((P[a] - 1) * spec.stride + spec.k[a] for a in range(3)) if spec.kind == 'conv' else P
+                for N in (2, 8, 32, 128):
+                    if N * D * H * W * max(spec.ci, spec.co) * (8 if spec.stride == 2 else 1) * 4 > 250e6:
+                        continue
+                    try:
+                        plan = ops.wgrad_plan(spec, *_wgrad_shapes(spec, isz, N), True, 1)
+                    except _lib.VgError:
+                        continue
+                    found.setdefault(wgrad_tuple(plan)[:7], (sname, isz, N))
+    return found
+
+
+def wgrad_coverage():
+    """What WGRAD_CASES, WGRAD_LOOP_CASES and WGRAD_GROUPED_CASES run against what the networks launch, from the plans alone
+    (nothing is launched; `grid`, `wave_slabs` and so the tuples are those of the library that is loaded)."""
+    cov = dict(production={}, cases={}, instances=set(), production_bpc={}, loop_case_bpc={}, accumulate=set(), wave_slabs=set(), nbuf=set(), PAD=set(), DSH=set(), partial_d=[], partial_h=[],
+               loops=[], loops_grouped=[])
+    for img, B, C, layer, plan in wgrad_production_plans():
+        cov['production'].setdefault(img, {}).setdefault(wgrad_tuple(plan), []).append('%s B%d C%d' % (layer, B, C))
+        cov['production_bpc'].setdefault(wgrad_tuple(plan), set()).add(plan.blocks_per_cu)
+    for cid, plan, accs, loop, grouped, pos in wgrad_case_plans():
+        if wgrad_tuple(plan)[-1] == int(loop):                      # a looping production launch is matched by loop cases only
+            cov['cases'].setdefault(wgrad_tuple(plan), []).append(cid)
+        cov['instances'].add(wgrad_tuple(plan)[:7])
+        if loop:
+            cov['loop_case_bpc'].setdefault(wgrad_tuple(plan)[:7], set()).add(plan.blocks_per_cu)
+        cov['accumulate'] |= accs; cov['wave_slabs'].add(plan.wave_slabs); cov['PAD'].add(plan.PAD); cov['DSH'].add(plan.DSH)
+        if plan.CA > 1:
+            cov['nbuf'].add('CA' if plan.nbuf == plan.CA else plan.nbuf)
+        looping = (plan.grp_items >= 2 * plan.ipb) if grouped else (plan.items >= 4097 and plan.items >= 2 * plan.grid)
+        assert looping == loop, (cid, plan)
+        if loop:
+            cov['loops_grouped' if grouped else 'loops'].append(cid)
+            if (pos[0] + plan.DSH) % plan.TPD:
+                cov['partial_d'].append(cid)
+            if pos[1] % plan.TPH:
+                cov['partial_h'].append(cid)
+    return cov
+
+
+# Production launches of the 82x98x70 network that may go unmatched, as (first seven tuple fields, reason) -- at most two.  Both are
+# 16-channel stride-2 layers whose production tile (3 x 8, 54,816 bytes of LDS) cannot be kept under the 256 MB limit at 4,097 items
+# (693 MB); the -small-tile cases run the same instance with 32,768 bytes.  The exemption holds only under the condition that causes
+# it: the occupancy query answers another number of blocks per CU for the case than for the production layer, so `wave_slabs` differs
+# (the host build, where the answer follows the LDS size: 2 against 5).  Where both get the same answer (the MI355X: 2, by registers)
+# the tuple must be covered like any other, so there nothing is left out.
+_F16S2 = (16, 3, 3, 3, 2, 0, 0)
+WGRAD_NOT_COVERED = (((_F16S2, 1, 4, 0, 0, 2, 2), 'conv4 of 82x98x70: production tile 693 MB at 4,097 items'),
+                     ((_F16S2, 0, 4, 0, 0, 2, 2), 'convt2 of 82x98x70: production tile 693 MB at 4,097 items'))
+
+
+def check_wgrad_coverage():
+    """the assertions of test_wgrad_case_matrix_coverage (shared by the host-build and the GPU suite)"""
+    cov = wgrad_coverage()
+    left = {t for t, _ in WGRAD_NOT_COVERED}
+    assert len(WGRAD_NOT_COVERED) <= 2
+    missed = []
+    for img, tuples in cov['production'].items():
+        for t, layers in tuples.items():
+            print('%s %r: %s <- %s' % ('x'.join(map(str, img)), t, ', '.join(layers), ', '.join(cov['cases'].get(t, [])) or 'NOT COVERED'))
+    for img, tuples in cov['production'].items():
+        for t, layers in tuples.items():
+            case_bpc = cov['loop_case_bpc'].get(t[:7], set())
+            if img == (82, 98, 70) and t[:7] in left and t not in cov['cases'] and case_bpc and case_bpc.isdisjoint(cov['production_bpc'][t]):
+                missed.append(t)
+                continue
+            assert t in cov['cases'], 'no listed case runs %r (%s: %s)' % (t, 'x'.join(map(str, img)), ', '.join(layers))
+    assert len(set(missed)) <= 2, missed
+    cov['left_out'] = sorted(set(missed))
+    print('left out: %r' % (cov['left_out'],))
+    # every instance and slot scheme the planner can select is run by a listed case
+    selectable = wgrad_selectable()
+    not_run = {t: ex for t, ex in selectable.items() if t not in cov['instances']}
+    assert not not_run, 'selectable, but run by no listed case: %r' % (not_run,)
+    cov['selectable'] = len(selectable)
+    assert cov['accumulate'] == {0, 1} and cov['wave_slabs'] == {0, 1} and cov['nbuf'] == {'CA', 2, 1}, cov
+    assert cov['PAD'] == {0, 1} and cov['DSH'] == {0, 1}
+    assert cov['partial_d'] and cov['partial_h'], (cov['partial_d'], cov['partial_h'])
+    assert len(cov['loops']) + len(cov['loops_grouped']) >= 6 and len(cov['loops_grouped']) >= 2
     return cov
 
 

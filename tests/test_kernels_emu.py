@@ -134,6 +134,56 @@ def test_conv_mm_case_matrix_coverage():
     assert cov['loops'] >= 4 and cov['loops_stats'] >= 2
 
 
+_HOST_WGRAD_CASES = [c for c in K.WGRAD_CASES + K.WGRAD_MID_CASES if c[0] not in K.WGRAD_GPU_ONLY]                   # the reason stands next to that list
+
+
+@pytest.mark.parametrize('case', _HOST_WGRAD_CASES, ids=[c[0] for c in _HOST_WGRAD_CASES])
+def test_wgrad_instances(case):
+    """every selectable instance and slot scheme of wgrad_rows_k, one item per block, written and accumulated, against float64"""
+    K.run_wgrad_instance_listed('cpu', case)
+
+
+_HOST_WGRAD_LOOPS = [c for c in K.WGRAD_LOOP_CASES if c[0] in K.WGRAD_LOOP_HOST]                 # the reason stands next to that list
+
+
+@pytest.mark.parametrize('case', _HOST_WGRAD_LOOPS, ids=[c[0] for c in _HOST_WGRAD_LOOPS])
+def test_wgrad_item_loop(case):
+    """persistent blocks walk several items: accumulators kept across items, scale / shift reloaded when the group changes, a short
+    tile followed by a full one in the same LDS, one slab per block"""
+    K.run_wgrad_loop_listed('cpu', case, seed=1)
+
+
+_HOST_WGRAD_GROUPED = [c for c in K.WGRAD_GROUPED_CASES if c[0] not in K.WGRAD_LOOP_GPU_ONLY]
+
+
+@pytest.mark.parametrize('case', _HOST_WGRAD_GROUPED, ids=[c[0] for c in _HOST_WGRAD_GROUPED])
+def test_wgrad_grouped(case):
+    """vg_wgrad3d_grouped: per-group partials and the row of per-tap sums, several items per block, then vg_bn_tconv1_sums"""
+    K.run_wgrad_grouped_listed('cpu', case, seed=2)
+
+
+def test_wgrad_case_matrix_coverage():
+    K.check_wgrad_coverage()
+
+
+@pytest.mark.parametrize('name', list(K.BOUND_LAYERS))
+def test_layer_bound_gradients(name):
+    """the backward adds straight into bound, prefilled .grad buffers: a stride-1 and a stride-2 conv layer, the padded convt2, convt4
+    and the fused last stage (dw through vg_bn_tconv1_sums)"""
+    idx, with_bn = K.BOUND_LAYERS[name]
+    lname, spec, isz = K.LAYERS[idx]
+    K.run_layer_case('cpu', lname, spec, isz, with_bn=with_bn, relu_in=True, groups=2, seed=21 + idx, bound_grads=True)
+
+
+def test_first_layer_input_is_data_bound_gradients():
+    name, spec, isz = K.LAYERS[0]
+    K.run_layer_case('cpu', name, spec, isz, with_bn=True, relu_in=False, groups=1, input_is_data=True, seed=5, bound_grads=True)
+
+
+def test_chain_producer_bias_handoff():
+    K.run_chain_case('cpu')
+
+
 def _layer_args(name, spec):
     """the arguments of test_layer_bn_relu / test_layer_wide_rows for this layer"""
     groups = 2 if spec.kind == 'convt' else 1

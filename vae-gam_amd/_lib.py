@@ -68,6 +68,7 @@ _PROTOS = {
     'vg_wgrad3d': (ctypes.c_int, [ctypes.POINTER(WgradDesc), vp, vp, vp, vp, vp, vp, i32, vp]),
     'vg_wgrad3d_grouped_ws_bytes': (i64, [ctypes.POINTER(WgradDesc)]),
     'vg_wgrad3d_grouped': (ctypes.c_int, [ctypes.POINTER(WgradDesc), vp, vp, vp, vp, vp, vp, vp]),
+    'vg_wgrad3d_plan': (ctypes.c_int, [ctypes.POINTER(WgradDesc), i32, ctypes.POINTER(i32), i32]),
     'vg_bn_tconv1_sums': (ctypes.c_int, [vp, vp, vp, vp, i32, i32, i32, vp, vp, i32, vp]),
     'vg_bn_ws_bytes': (i64, [i32, i32, i64, i32]),
     'vg_bn_stats': (ctypes.c_int, [vp, i32, i32, i64, i32, i32, vp, vp, f32, vp, vp, vp, vp, vp, vp, vp]),
@@ -113,6 +114,8 @@ _PROTOS = {
     'vg_adam_step_guarded': (ctypes.c_int, [vp, vp, vp, vp, i64, i32, f64, f64, f64, vp, vp, vp]),
     'vg_volume_gather': (ctypes.c_int, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, f64, vp, vp]),
 }
+WGRAD_PLAN_FIELDS = ('CA', 'KD', 'KH', 'KW', 'stride', 'PAD', 'DSH', 'PA', 'UG', 'RES', 'GRP', 'ONE', 'TPD', 'TPH', 'nbuf', 'pdblocks', 'nph',
+                     'items', 'grid', 'wave_slabs', 'ipb', 'grp_items', 'nslabs', 'lds_bytes', 'blocks_per_cu')    # VG_WGRAD_PLAN_LEN, in order
 GUARD_STATE_LEN = 8            # VG_GUARD_STATE_LEN: [total_norm, scale, apply, seen, skipped, clipped, norm_sum, norm_max]
 EXPORTS = tuple(_PROTOS)
 

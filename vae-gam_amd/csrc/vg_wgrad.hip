@@ -419,10 +419,13 @@ constexpr bool rows_instance(bool pa, int ug, bool res, bool grp, int one) {
     return (ug == 4 && !res) || (CA > 1 && !DSH && ug == 2 && res);      // one == 2, 3
 }
 
+// What a query call (no launch) wants back from launch_rows: the workspace size, the plan record of vg_wgrad3d_plan, or both
+struct RowsQuery { int64_t* ws_bytes; int32_t* plan; };
+
 // returns -1 when it has no plan or no instance for the descriptor (the caller reports VG_ERR_UNSUPPORTED)
 template <int CA, int TC, int KD, int KH, int KW, int S, bool PAD, bool DSH = false>
 int launch_rows(const vg_wgrad_desc* d, const float* a, const float* b, const float* in_scale, const float* in_shift,
-                float* ws, float* dw, hipStream_t s, int64_t* ws_bytes_only, int accumulate, int grouped) {
+                float* ws, float* dw, hipStream_t s, const RowsQuery* query, int accumulate, int grouped) {
     constexpr int KVOL = KD * KH * KW;
     constexpr int NT = CA * TC;
     constexpr int KDW = DSH ? KD - S : KD;                              // window planes a position touches (DSH: taps kd' in [S, KD) only)
@@ -518,7 +521,16 @@ int launch_rows(const vg_wgrad_desc* d, const float* a, const float* b, const fl
     p.wave_slabs = grid <= 512 ? 1 : 0;
     const int per_slab = p.wave_slabs ? 4 : 1;
     const int nslabs = grid * per_slab;
-    if (ws_bytes_only) { *ws_bytes_only = (int64_t)nslabs * len * sizeof(float); return VG_OK; }
+    if (query) {                                            // nothing is launched: the sizes and choices the launch below would use
+        if (query->ws_bytes) *query->ws_bytes = (int64_t)nslabs * len * sizeof(float);
+        if (query->plan) {
+            const int32_t rec[VG_WGRAD_PLAN_LEN] = {
+                CA, KD, KH, KW, S, PAD ? 1 : 0, DSH ? 1 : 0, pa ? 1 : 0, ug, res ? 1 : 0, grp ? 1 : 0, one, p.TPD, p.TPH, p.nbuf,
+                p.pdblocks, p.nph, p.items, grid, p.wave_slabs, p.ipb, p.grp_items, nslabs, (int32_t)(fl * sizeof(float)), per_cu};
+            for (int i = 0; i < VG_WGRAD_PLAN_LEN; ++i) query->plan[i] = rec[i];
+        }
+        return VG_OK;
+    }
     vg_launch(kern, dim3(grid), dim3(256), fl * sizeof(float), s, a, b, in_scale, in_shift, ws, p);
     int rc = vg_check_launch("wgrad_rows");
     if (rc) return rc;
@@ -532,7 +544,7 @@ int launch_rows(const vg_wgrad_desc* d, const float* a, const float* b, const fl
 }
 
 int dispatch(const vg_wgrad_desc* d, const float* a, const float* b, const float* in_scale, const float* in_shift,
-             float* ws, float* dw, hipStream_t s, int64_t* ws_only, int accumulate) {
+             float* ws, float* dw, hipStream_t s, const RowsQuery* ws_only, int accumulate) {
     if (!d) { vg_set_error("vg_wgrad3d: null descriptor"); return VG_ERR_ARG; }
     if (d->N <= 0 || d->CA <= 0 || d->CB <= 0 || d->PD <= 0 || d->PH <= 0 || d->PW <= 0 || d->AD <= 0 || d->AH <= 0 ||
         d->AW <= 0 || (d->stride != 1 && d->stride != 2)) {
@@ -567,7 +579,7 @@ int dispatch(const vg_wgrad_desc* d, const float* a, const float* b, const float
 }  // namespace
 
 static int grouped_dispatch(const vg_wgrad_desc* d, const float* a, const float* b, const float* in_scale, const float* in_shift,
-                            float* ws, float* out, hipStream_t s, int64_t* ws_only) {
+                            float* ws, float* out, hipStream_t s, const RowsQuery* ws_only) {
     if (!d) { vg_set_error("vg_wgrad3d_grouped: null descriptor"); return VG_ERR_ARG; }
     if (d->N <= 0 || d->per_group <= 0 || d->N % d->per_group || d->CB <= 0 || d->CB >= 16 || d->PD <= 0 || d->PH <= 0 || d->PW <= 0) {
         vg_set_error("vg_wgrad3d_grouped: bad shape"); return VG_ERR_ARG;
@@ -583,7 +595,8 @@ static int grouped_dispatch(const vg_wgrad_desc* d, const float* a, const float*
 
 extern "C" int64_t vg_wgrad3d_grouped_ws_bytes(const vg_wgrad_desc* d) {
     int64_t bytes = 0;
-    int rc = grouped_dispatch(d, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &bytes);
+    const RowsQuery q = {&bytes, nullptr};
+    int rc = grouped_dispatch(d, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &q);
     return rc ? -1 : bytes;
 }
 
@@ -595,7 +608,8 @@ extern "C" int vg_wgrad3d_grouped(const vg_wgrad_desc* d, const float* a, const 
 
 extern "C" int64_t vg_wgrad3d_ws_bytes(const vg_wgrad_desc* d) {
     int64_t bytes = 0;
-    int rc = dispatch(d, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &bytes, 0);
+    const RowsQuery q = {&bytes, nullptr};
+    int rc = dispatch(d, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &q, 0);
     return rc ? -1 : bytes;
 }
 
@@ -603,4 +617,11 @@ extern "C" int vg_wgrad3d(const vg_wgrad_desc* d, const float* a, const float* b
                           const float* in_shift, float* ws, float* dw, int32_t accumulate, void* stream) {
     if (!a || !b || !ws || !dw) { vg_set_error("vg_wgrad3d: null argument"); return VG_ERR_ARG; }
     return dispatch(d, a, b, in_scale, in_shift, ws, dw, (hipStream_t)stream, nullptr, accumulate);
+}
+
+extern "C" int vg_wgrad3d_plan(const vg_wgrad_desc* d, int32_t grouped, int32_t* out, int32_t n_out) {
+    if (!out || n_out < VG_WGRAD_PLAN_LEN) { vg_set_error("vg_wgrad3d_plan: out must hold VG_WGRAD_PLAN_LEN values"); return VG_ERR_ARG; }
+    const RowsQuery q = {nullptr, out};
+    if (grouped) return grouped_dispatch(d, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &q);
+    return dispatch(d, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &q, 0);
 }

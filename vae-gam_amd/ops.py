@@ -11,6 +11,7 @@ and the batch-norm affine while loading (`relu_in`, `gamma`/`beta`).  This remov
 stand-alone ReLU / batch-norm-apply pass of the reference graph (vae_reg_GP.py:238-264).
 """
 import ctypes
+from collections import namedtuple
 from dataclasses import dataclass
 from typing import Optional, Tuple
 
@@ -298,20 +299,37 @@ def conv_backward_data(dy, wpk_bwd, spec: ConvSpec, in_size, mask_src=None):
     return dx
 
 
+def wgrad_desc(spec: ConvSpec, x_shape, dy_shape, relu_in=False, per_group=1):
+    """The vg_wgrad_desc of a layer's weight gradient (x: the layer's input, dy: the gradient of its output)
+    -> (descriptor, window tensor is x, shape of dw).  Conv3d: positions = dy, windows = x (prologue on the windows);
+    ConvTranspose3d: positions = x (prologue on the positions), windows = dy."""
+    N = int(x_shape[0])
+    isz = tuple(int(v) for v in x_shape[2:]); osz = tuple(int(v) for v in dy_shape[2:])
+    if spec.kind == 'conv':
+        d = WgradDesc(N, spec.co, spec.ci, *osz, *isz, *spec.k, spec.stride, 0, 0, 0, 1, int(relu_in), int(per_group))
+        return d, True, (spec.co, spec.ci) + tuple(spec.k)
+    d = WgradDesc(N, spec.ci, spec.co, *isz, *osz, *spec.k, spec.stride, *spec.pad, 0, int(relu_in), int(per_group))
+    return d, False, (spec.ci, spec.co) + tuple(spec.k)
+
+
+WgradPlan = namedtuple('WgradPlan', _lib.WGRAD_PLAN_FIELDS)
+
+
+def wgrad_plan(spec: ConvSpec, x_shape, dy_shape, relu_in=False, per_group=1, grouped=False) -> WgradPlan:
+    """What vg_wgrad3d (grouped: vg_wgrad3d_grouped) would launch for this layer's weight gradient, from the library's own
+    planner (vg_wgrad3d_plan): nothing is launched, shapes only."""
+    d, _, _ = wgrad_desc(spec, x_shape, dy_shape, relu_in, per_group)
+    rec = (ctypes.c_int32 * len(WgradPlan._fields))()
+    _lib.get_lib().call('vg_wgrad3d_plan', ctypes.byref(d), int(bool(grouped)), rec, len(rec))
+    return WgradPlan(*rec)
+
+
 def conv_weight_grad(x, dy, spec: ConvSpec, relu_in=False, scale=None, shift=None, per_group=1, out=None):
     """dL/dW in the layer's own weight layout; the prologue of the forward is re-applied to x on load."""
     lib = _lib.get_lib()
-    N = x.shape[0]
-    isz = tuple(x.shape[2:]); osz = tuple(dy.shape[2:])
     _chk(x); _chk(dy)
-    if spec.kind == 'conv':
-        d = WgradDesc(N, spec.co, spec.ci, *osz, *isz, *spec.k, spec.stride, 0, 0, 0, 1, int(relu_in), int(per_group))
-        a, b = x, dy
-        shape = (spec.co, spec.ci) + tuple(spec.k)
-    else:
-        d = WgradDesc(N, spec.ci, spec.co, *isz, *osz, *spec.k, spec.stride, *spec.pad, 0, int(relu_in), int(per_group))
-        a, b = dy, x
-        shape = (spec.ci, spec.co) + tuple(spec.k)
+    d, a_is_x, shape = wgrad_desc(spec, x.shape, dy.shape, relu_in, per_group)
+    a, b = (x, dy) if a_is_x else (dy, x)
     nbytes = lib.size('vg_wgrad3d_ws_bytes', ctypes.byref(d))
     ws = torch.empty(max(nbytes // 4, 1), dtype=torch.float32, device=x.device)
     if out is not None:          # accumulate straight into the parameter's .grad (a view of the flat gradient buffer)
@@ -415,12 +433,40 @@ def bn_backward_(dxe, p, gamma, mean, rstd, relu, per_group, sync=None, beta=Non
 _GROUPED_OK = {}
 
 
+def _last_stage(C):
+    """the decoder's last stage: C -> 1 channels, 3x3x3 stride-1 transposed conv"""
+    return ConvSpec('convt', C, 1, (3, 3, 3), 1)
+
+
+def wgrad_grouped(dy, p, in_scale, in_shift, relu, per_group):
+    """vg_wgrad3d_grouped for the last decoder stage: dy [N][1][D+2][H+2][W+2], p [N][C][D][H][W] -> q [G][C+1][27]: per batch-norm
+    group the weight gradient against relu?(p) * in_scale + in_shift (rows c < C) and the per-tap sums of dy (row C)."""
+    lib = _lib.get_lib()
+    N, C = p.shape[0], p.shape[1]
+    _chk(dy); _chk(p)
+    d, _, _ = wgrad_desc(_last_stage(C), p.shape, dy.shape, relu, per_group)
+    nbytes = lib.size('vg_wgrad3d_grouped_ws_bytes', ctypes.byref(d))
+    wws = torch.empty(max(nbytes // 4, 1), dtype=torch.float32, device=p.device)
+    q = torch.empty((N // per_group, C + 1, 27), dtype=torch.float32, device=p.device)
+    _call(p, 'vg_wgrad3d_grouped', ctypes.byref(d), _p(dy), _p(p), _p(_chk(in_scale)), _p(_chk(in_shift)), _p(wws), _p(q))
+    return q
+
+
+def bn_tconv1_sums(q, w, gamma, beta, dw, accumulate):
+    """vg_bn_tconv1_sums: q [G][C+1][27] of wgrad_grouped (taken against the normalised activation) -> sums double[G*C][2] =
+    {sum dxe, sum dxe * hhat}; dw [C][1][3][3][3] (the conv's weight gradient) written, or added to when `accumulate`."""
+    G, C1, K = q.shape
+    sums = torch.empty((G * (C1 - 1), 2), dtype=torch.float64, device=q.device)
+    _call(q, 'vg_bn_tconv1_sums', _p(_chk(q)), _p(_chk(w)), _p(gamma), _p(beta), G, C1 - 1, K, _p(sums), _p(dw), int(bool(accumulate)))
+    return sums
+
+
 def _grouped_wgrad_ok(p_shape, per_group):
     """Whether vg_wgrad3d_grouped has an instance for the last decoder stage at this geometry (asked once per shape)."""
     key = (tuple(p_shape), int(per_group))
     if key not in _GROUPED_OK:
         N, C, ID, IH, IW = key[0]
-        d = WgradDesc(N, C, 1, ID, IH, IW, ID + 2, IH + 2, IW + 2, 3, 3, 3, 1, 0, 0, 0, 0, 0, int(per_group))
+        d, _, _ = wgrad_desc(_last_stage(C), key[0], (N, 1, ID + 2, IH + 2, IW + 2), False, per_group)
         _GROUPED_OK[key] = _lib.get_lib().dll.vg_wgrad3d_grouped_ws_bytes(ctypes.byref(d)) >= 0
     return _GROUPED_OK[key]
 
@@ -442,17 +488,12 @@ def bn_backward_tconv1(dy, weight, p, gamma, mean, rstd, relu, per_group, sync=N
     G = N // per_group
     P = ID * IH * IW
     ws = torch.empty(lib.size('vg_bn_tconv1_ws_bytes', N, C, ID, per_group) // 8, dtype=torch.float64, device=p.device)
-    sums = torch.empty((G * C, 2), dtype=torch.float64, device=p.device)
     if dw_out is not None:
         assert dw_out.shape == weight.shape and dw_out.is_contiguous() and dw_out.dtype == torch.float32 and beta is not None
-        d = WgradDesc(N, C, 1, ID, IH, IW, ID + 2, IH + 2, IW + 2, 3, 3, 3, 1, 0, 0, 0, 0, int(relu), int(per_group))
-        nbytes = lib.size('vg_wgrad3d_grouped_ws_bytes', ctypes.byref(d))
-        wws = torch.empty(nbytes // 4, dtype=torch.float32, device=p.device)
-        q = torch.empty((G, C + 1, 27), dtype=torch.float32, device=p.device)
-        nshift = -(mean * rstd)
-        _call(p, 'vg_wgrad3d_grouped', ctypes.byref(d), _p(dy), _p(p), _p(rstd), _p(nshift), _p(wws), _p(q))
-        _call(p, 'vg_bn_tconv1_sums', _p(q), _p(w), _p(gamma), _p(beta), G, C, 27, _p(sums), _p(dw_out), 1)
+        q = wgrad_grouped(dy, p, rstd, -(mean * rstd), relu, per_group)
+        sums = bn_tconv1_sums(q, w, gamma, beta, dw_out, True)
     else:
+        sums = torch.empty((G * C, 2), dtype=torch.float64, device=p.device)
         _call(p, 'vg_bn_bwd_reduce_tconv1', _p(dy), _p(w), _p(p), N, C, ID, IH, IW, per_group, int(relu), _p(mean), _p(rstd), _p(ws), _p(sums))
     count = float(per_group * P)
     local = None
