@@ -9,6 +9,11 @@
  *   - return value: 0 = OK, non-zero = vg_status; text via vg_last_error(); no exceptions;
  *   - activations are fp32, NCDHW, contiguous.  Layers store PRE-activation values; the
  *     consumer applies ReLU and the batch-norm affine when it loads them (`vg_prologue`).
+ *     Rectified hand-off: a forward launch with `relu_out` set stores max(y, 0) instead.  Every
+ *     consumer of such a tensor rectifies it or tests its sign (relu(relu(p)) == relu(p),
+ *     relu(p) > 0 <=> p > 0), so nothing downstream changes by a bit, and a consumer without a
+ *     batch-norm affine may then be launched with relu_in = 0, i.e. without any prologue.
+ *     Statistics partials (stats_relu = 1) are the same with and without relu_out.
  *   - "group": the decoder runs C+1 one-hot variants in one launch (sample n -> group
  *     n / per_group); batch-norm statistics are kept per group (vae_reg_GP.py:330,343 call
  *     decode() separately per variant, each with its own batch statistics).
@@ -30,6 +35,7 @@ typedef struct vg_conv_desc {
     int32_t pad_d, pad_h, pad_w; /* corr: leading zero padding of the input; tconv: ConvTranspose3d padding */
     int32_t relu_in;           /* prologue: max(x,0) on load */
     int32_t per_group;         /* samples per affine group for in_scale/in_shift ([N/per_group][CI]) */
+    int32_t relu_out;          /* forward launches: store max(y, 0) instead of y (see "rectified hand-off" below); ignored with mask_src */
 } vg_conv_desc;
 
 /* library identity / errors */
@@ -87,6 +93,7 @@ typedef struct vg_mm_desc {
     int32_t PHB;               /* position rows per block (a block = PD planes x PHB rows x PW columns); 0 or >= PH: whole planes */
     int32_t hlo, hhi;          /* smallest / largest row offset dh in the window-offset table: which input rows a row slab stages */
     int32_t waves;             /* wavefronts per workgroup: 8 or 4 (4: half the tile, twice the co-resident workgroups per CU) */
+    int32_t relu_out;          /* as vg_conv_desc.relu_out */
 } vg_mm_desc;
 int64_t vg_conv_mm_stats_chunks(const vg_mm_desc* d, int32_t stats_per_group);
 int vg_conv_mm(const vg_mm_desc* d, const float* x, const float* a_img, const int32_t* tau, const int32_t* dlt, const float* bias,

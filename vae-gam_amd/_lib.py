@@ -20,7 +20,7 @@ i32, i64, f32, f64, vp = ctypes.c_int32, ctypes.c_int64, ctypes.c_float, ctypes.
 
 class ConvDesc(ctypes.Structure):
     _fields_ = [(n, i32) for n in ('N', 'CI', 'CO', 'ID', 'IH', 'IW', 'OD', 'OH', 'OW', 'KD', 'KH', 'KW',
-                                   'stride', 'pad_d', 'pad_h', 'pad_w', 'relu_in', 'per_group')]
+                                   'stride', 'pad_d', 'pad_h', 'pad_w', 'relu_in', 'per_group', 'relu_out')]
 
 
 class WgradDesc(ctypes.Structure):
@@ -31,7 +31,8 @@ class WgradDesc(ctypes.Structure):
 class MmDesc(ctypes.Structure):
     _fields_ = [(n, i32) for n in ('N', 'CI', 'CO', 'ID', 'IH', 'IW', 'OD', 'OH', 'OW', 'nq')] + [('ks', i32 * 4)] + \
                [(n, i32) for n in ('PDT', 'PH', 'PW', 'PD', 'sdi', 'shi', 'swi', 'd0', 'LD', 'cc', 'sdo', 'sho', 'swo')] + \
-               [('od0', i32 * 4), ('oh0', i32 * 4), ('ow0', i32 * 4)] + [(n, i32) for n in ('relu_in', 'per_group', 'tpc', 'slack', 'dbuf', 'PHB', 'hlo', 'hhi', 'waves')]
+               [('od0', i32 * 4), ('oh0', i32 * 4), ('ow0', i32 * 4)] + [(n, i32) for n in ('relu_in', 'per_group', 'tpc', 'slack', 'dbuf', 'PHB', 'hlo', 'hhi', 'waves',
+                                                                                         'relu_out')]
 
 
 class GainDesc(ctypes.Structure):

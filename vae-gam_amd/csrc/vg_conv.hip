@@ -153,6 +153,7 @@ corr3d_direct_k(const float* __restrict__ x, const float* __restrict__ wpk, cons
         }
     }
     const size_t plane = (size_t)d.OH * d.OW;
+    const bool relu_out = d.relu_out && !mask_src;      // rectified storage is a forward hand-off: a masked (data-gradient) store ignores it
     // fused ReLU backward of the producer: fetch all mask values first (clamped, unconditional loads that
     // stay in flight together), then apply + store
     if (mask_src) {
@@ -194,7 +195,9 @@ corr3d_direct_k(const float* __restrict__ x, const float* __restrict__ wpk, cons
                     const int ow = ow_t + j;
                     if (ow < d.OW) {
                         const float v = acc[a][b][j][co];
-                        y[base + ow] = (v == -__builtin_inff()) ? 0.f : v + bv;
+                        float o = (v == -__builtin_inff()) ? 0.f : v + bv;
+                        if (relu_out) o = vg_max(o, 0.f);
+                        y[base + ow] = o;
                     }
                 }
             }
@@ -428,6 +431,7 @@ corr3d_plane_k(const float* __restrict__ x, const float* __restrict__ wpk, const
     }
     if (!active) return;
     const size_t oplane = (size_t)d.OH * d.OW;
+    const bool relu_out = d.relu_out && !mask_src;
     if (mask_src) {
 #pragma unroll
         for (int a = 0; a < TDt; ++a) {
@@ -467,7 +471,9 @@ corr3d_plane_k(const float* __restrict__ x, const float* __restrict__ wpk, const
                     const int ow = ow_t + j;
                     if (ow < d.OW) {
                         const float v = acc[a][b][j][co];
-                        y[base + ow] = (v == -__builtin_inff()) ? 0.f : v + bv;
+                        float o = (v == -__builtin_inff()) ? 0.f : v + bv;
+                        if (relu_out) o = vg_max(o, 0.f);
+                        y[base + ow] = o;
                     }
                 }
             }
@@ -552,7 +558,9 @@ struct TconvParams {
     int JD, JH, JW;             // number of j positions per dim
 };
 
-template <int COT, int KD, int KH, int KW, int COC>
+// NOPRO: no ReLU / affine on the input (data gradients, and forwards whose producer stored its output rectified): the window
+// elements are used as loaded -- 2 of the 2 + 13.5 vector instructions an element costs in the 3x3x3 16-channel instance
+template <int COT, int KD, int KH, int KW, int COC, bool NOPRO = false>
 __global__ void __launch_bounds__(256, 4)
 tconv3d_s2_k(const float* __restrict__ x, const float* __restrict__ wpk, const float* __restrict__ bias,
              const float* __restrict__ in_scale, const float* __restrict__ in_shift,
@@ -629,7 +637,7 @@ tconv3d_s2_k(const float* __restrict__ x, const float* __restrict__ wpk, const f
             for (int mh = 0; mh < MH; ++mh)
 #pragma unroll
                 for (int mw = 0; mw < MW; ++mw) {
-                    const float v = fmaf(vg_max(nxt[md][mh][mw], lo), sc, sh);
+                    const float v = NOPRO ? nxt[md][mh][mw] : fmaf(vg_max(nxt[md][mh][mw], lo), sc, sh);
                     xin[md][mh][mw] = (rok[md][mh] && cok[mw]) ? v : 0.f;
                     nxt[md][mh][mw] = xn[roff[md][mh] + cof[mw]];
                 }
@@ -684,6 +692,7 @@ tconv3d_s2_k(const float* __restrict__ x, const float* __restrict__ wpk, const f
             }
         }
     }
+    const bool relu_out = d.relu_out && !mask_src;
     float st_s[COT], st_q[COT];                       // optional: sum / sum of squares of relu?(y) per channel (next layer's BN)
 #pragma unroll
     for (int co = 0; co < COT; ++co) { st_s[co] = 0.f; st_q[co] = 0.f; }
@@ -705,11 +714,13 @@ tconv3d_s2_k(const float* __restrict__ x, const float* __restrict__ wpk, const f
 #pragma unroll
                 for (int rw = 0; rw < 2; ++rw) {
                     const float v = acc[rd][rh][rw][co];
-                    o2[rw] = (v == -__builtin_inff()) ? 0.f : v + bv;
+                    const float o = (v == -__builtin_inff()) ? 0.f : v + bv;
+                    const float orl = vg_max(o, 0.f);
                     if (ow0 + rw >= 0 && ow0 + rw < d.OW) {
-                        const float h = stats_relu ? vg_max(o2[rw], 0.f) : o2[rw];
+                        const float h = stats_relu ? orl : o;                     // the same value whether or not it is also what is stored
                         st_s[co] += h; st_q[co] = fmaf(h, h, st_q[co]);
                     }
+                    o2[rw] = relu_out ? orl : o;
                 }
                 if (ow0 >= 0 && ow0 + 1 < d.OW) vg_store2(y + base + ow0, o2[0], o2[1]);
                 else {
@@ -755,8 +766,12 @@ int launch_tconv(const vg_conv_desc* d, const float* x, const float* wpk, const 
     const int threads = vg_cdiv(p.TJW * p.TJH * p.TJD, VG_WAVE) * VG_WAVE;
     dim3 grid(p.tilesW * p.tilesH * p.tilesD, d->N, d->CO / COT);
     if (chunks_only) { *chunks_only = (int64_t)stats_pg * grid.x * (threads / VG_WAVE); return VG_OK; }
-    vg_launch(tconv3d_s2_k<COT, KD, KH, KW, COC>, grid, dim3(threads), 0, s,
-              x, wpk, bias, in_scale, in_shift, mask_src, y, p, stats_part, stats_relu, stats_pg);
+    if (in_scale == nullptr && !d->relu_in)
+        vg_launch(tconv3d_s2_k<COT, KD, KH, KW, COC, true>, grid, dim3(threads), 0, s,
+                  x, wpk, bias, in_scale, in_shift, mask_src, y, p, stats_part, stats_relu, stats_pg);
+    else
+        vg_launch(tconv3d_s2_k<COT, KD, KH, KW, COC>, grid, dim3(threads), 0, s,
+                  x, wpk, bias, in_scale, in_shift, mask_src, y, p, stats_part, stats_relu, stats_pg);
     return vg_check_launch("tconv3d_s2");
 }
 

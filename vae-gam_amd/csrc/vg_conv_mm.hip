@@ -240,6 +240,8 @@ conv_mm_k(const float* __restrict__ x, const float* __restrict__ a_img, const in
                     if constexpr (NQ == 1) v = (mreg[i][r] > 0.f) ? v : 0.f;                       // fetched before the matrix phase
                     else v = (*reinterpret_cast<const float*>(mn + (size_t)r * ovol * 4 + off) > 0.f) ? v : 0.f;
                 }
+                const float vraw = v, vr = vg_max(v, 0.f);
+                if constexpr (!MASKED) { if (d.relu_out) v = vr; }       // rectified storage (a forward hand-off; masked stores ignore it)
 #if defined(VG_ABLATE_STORE) && VG_ABLATE_STORE == 1
                 if (v == 1.2345e-30f) *reinterpret_cast<float*>(yn + (size_t)r * ovol * 4 + off) = v;        // diagnostic: (almost) no store
 #elif defined(VG_ABLATE_STORE) && VG_ABLATE_STORE == 2
@@ -254,7 +256,7 @@ conv_mm_k(const float* __restrict__ x, const float* __restrict__ a_img, const in
                 *reinterpret_cast<float*>(yn + (size_t)r * ovol * 4 + off) = v;
 #endif
                 if (stats_part) {
-                    const float h = stats_relu ? vg_max(v, 0.f) : v;
+                    const float h = stats_relu ? vr : vraw;                 // the same partials whether or not vr is also what is stored
                     st_s[r] += h; st_q[r] = fmaf(h, h, st_q[r]);
                 }
             }
@@ -479,8 +481,6 @@ static int mm_plan_params(const vg_mm_desc* d, MmParams* p, size_t* shmem, const
         vg_set_error("%s: bad descriptor", who); return VG_ERR_ARG;
     }
     p->d = *d;
-    int ns = 256 / p->bps; if (ns < 1) ns = 1; if (ns > d->N) ns = d->N;
-    p->nsplit = ns;
     int row = 0, af = 0;
     for (int q = 0; q < d->nq; ++q) {
         if (d->ks[q] <= 0 || d->ks[q] > 32) { vg_set_error("%s: k-steps per channel must be 1..32 (class %d: %d)", who, q, d->ks[q]); return VG_ERR_ARG; }
@@ -525,7 +525,7 @@ extern "C" int64_t vg_conv_mm_stats_chunks(const vg_mm_desc* d, int32_t stats_pe
 extern "C" int vg_conv_mm(const vg_mm_desc* d, const float* x, const float* a_img, const int32_t* tau, const int32_t* dlt,
                           const float* bias, const float* in_scale, const float* in_shift, const float* mask_src, float* y,
                           int32_t stats_per_group, int32_t stats_relu, double* stats_part, void* stream) {
-    MmParams p; size_t shmem;
+    MmParams p{}; size_t shmem;
     int rc = mm_plan_params(d, &p, &shmem, "vg_conv_mm");
     if (rc) return rc;
     if (!x || !a_img || !tau || !dlt || !y) { vg_set_error("vg_conv_mm: null argument"); return VG_ERR_ARG; }

@@ -9,6 +9,9 @@ their backward passes are explicit kernel sequences, not autograd traces.
 Storage convention: a layer stores its PRE-activation output; the consumer applies the ReLU
 and the batch-norm affine while loading (`relu_in`, `gamma`/`beta`).  This removes every
 stand-alone ReLU / batch-norm-apply pass of the reference graph (vae_reg_GP.py:238-264).
+Where every consumer of an activation rectifies it anyway (the decoder), the producer may store
+max(y, 0) instead and the consumer is told so (`BnConvAct`: relu_out / rectified_in): the same bits
+downstream, and a consumer without a batch norm then runs without any prologue.
 """
 import ctypes
 from collections import namedtuple
@@ -239,13 +242,14 @@ class PackedWeights:
         return self._views[(name, direction)]
 
 
-def _conv_desc(N, ci, co, isz, osz, k, stride, pad, relu_in, per_group):
+def _conv_desc(N, ci, co, isz, osz, k, stride, pad, relu_in, per_group, relu_out=False):
     return ConvDesc(N, ci, co, isz[0], isz[1], isz[2], osz[0], osz[1], osz[2], k[0], k[1], k[2], stride,
-                    pad[0], pad[1], pad[2], int(relu_in), int(per_group))
+                    pad[0], pad[1], pad[2], int(relu_in), int(per_group), int(bool(relu_out)))
 
 
-def conv_forward(x, wpk, bias, spec: ConvSpec, relu_in=False, scale=None, shift=None, per_group=1, next_bn=None):
-    """Layer forward: y = conv/convT(P(x)) + bias, y is the pre-activation.
+def conv_forward(x, wpk, bias, spec: ConvSpec, relu_in=False, scale=None, shift=None, per_group=1, next_bn=None, relu_out=False):
+    """Layer forward: y = conv/convT(P(x)) + bias, y is the pre-activation -- or, with relu_out, max(y, 0) (the rectified hand-off
+    of BnConvAct; the statistics partials of next_bn are the same either way).
     next_bn = per_group of the BatchNorm3d that consumes relu(y): the stride-2 transposed-conv kernel then also accumulates
     the statistics partials for it (no separate pass over y) and the call returns (y, partials) -- the caller hands the
     partials to the consuming layer's bn_stats(pre=...) explicitly."""
@@ -256,14 +260,14 @@ def conv_forward(x, wpk, bias, spec: ConvSpec, relu_in=False, scale=None, shift=
     _chk(x); _chk(wpk)
     if spec.kind == 'conv':
         assert spec.pad == (0, 0, 0)
-        d = _conv_desc(N, spec.ci, spec.co, isz, osz, spec.k, spec.stride, (0, 0, 0), relu_in, per_group)
+        d = _conv_desc(N, spec.ci, spec.co, isz, osz, spec.k, spec.stride, (0, 0, 0), relu_in, per_group, relu_out)
         _call(x, 'vg_corr3d', ctypes.byref(d), _p(x), _p(wpk), _p(bias), _p(scale), _p(shift), None, _p(y))
     elif spec.stride == 1:
         padc = tuple(spec.k[a] - 1 - spec.pad[a] for a in range(3))
-        d = _conv_desc(N, spec.ci, spec.co, isz, osz, spec.k, 1, padc, relu_in, per_group)
+        d = _conv_desc(N, spec.ci, spec.co, isz, osz, spec.k, 1, padc, relu_in, per_group, relu_out)
         _call(x, 'vg_corr3d', ctypes.byref(d), _p(x), _p(wpk), _p(bias), _p(scale), _p(shift), None, _p(y))
     else:
-        d = _conv_desc(N, spec.ci, spec.co, isz, osz, spec.k, 2, spec.pad, relu_in, per_group)
+        d = _conv_desc(N, spec.ci, spec.co, isz, osz, spec.k, 2, spec.pad, relu_in, per_group, relu_out)
         if next_bn:
             chunks = lib.size('vg_tconv3d_s2_stats_chunks', ctypes.byref(d), int(next_bn))
             G = N // int(next_bn)
@@ -532,7 +536,7 @@ def channel_sum(x, out=None):
 
 # --------------------------------------------------------------------------- autograd nodes
 class BnConvAct(torch.autograd.Function):
-    """y = conv( BN( relu?(p_in) ) ) + bias, everything stored pre-activation.
+    """y = conv( BN( relu?(p_in) ) ) + bias, stored pre-activation -- or rectified, where the layers agree on it (below).
 
     forward  : [bn_stats] -> corr3d / tconv3d_s2 with the ReLU + affine applied while staging tiles
     backward : channel_sum (bias), wgrad3d, data gradient (+ fused ReLU mask), [bn backward]
@@ -546,14 +550,23 @@ class BnConvAct(torch.autograd.Function):
       backward  `producer_bias` : Parameter (bias of the layer that produced p_in).  This layer's batch-norm backward adds
                               the per-channel sum of the gradient it hands back straight into producer_bias.grad, and the
                               producing layer is built with `bias_grad_by_consumer=True` so that it skips its own pass.
+      forward   `relu_out`  : this layer stores max(y, 0) instead of y.  Legal exactly where EVERY consumer of y rectifies it or only tests
+                              its sign (the next layer's forward, weight gradient, ReLU mask, batch-norm statistics and backward all do):
+                              relu(relu(y)) == relu(y) and relu(y) > 0 <=> y > 0, so no bit downstream changes.  The consuming layer
+                              is built with `rectified_in=True`: `relu_in` keeps its mathematical meaning (the backward still masks
+                              by p_in > 0), only the forward LAUNCH is told that the max is already done -- without a batch norm it
+                              then has no prologue at all.
     """
 
     @staticmethod
     def forward(ctx, p_in, weight, bias, gamma, beta, spec: ConvSpec, relu_in: bool, per_group: int,
                 input_is_data: bool, sync, packed=None, next_bn=None, pre_stats=None, producer_bias=None,
-                bias_grad_by_consumer=False):
+                bias_grad_by_consumer=False, relu_out=False, rectified_in=False):
         p_in = p_in.contiguous()
         has_bn = gamma is not None
+        assert not rectified_in or relu_in, 'rectified_in: p_in = relu(p) only stands in for p where the layer rectifies its input'
+        # what the forward launch is told: a rectified input without an affine needs no prologue; with one the max stays (harmless)
+        fwd_relu = relu_in and not (rectified_in and not has_bn)
         assert producer_bias is None or has_bn, 'producer_bias: the hand-off happens in the batch-norm backward'
         scale = shift = mean = rstd = None
         part = None
@@ -562,10 +575,10 @@ class BnConvAct(torch.autograd.Function):
                 scale, shift, mean, rstd = bn_stats(p_in, gamma, beta, relu_in, per_group, sync, pre_stats)
             mmf = _mm_for(packed, weight, spec, 'fwd', tuple(p_in.shape[2:]), None)
             if mmf is not None:
-                y = conv_mm(p_in, mmf[0], mmf[1], bias, relu_in, scale, shift, per_group, None, next_bn)
+                y = conv_mm(p_in, mmf[0], mmf[1], bias, fwd_relu, scale, shift, per_group, None, next_bn, relu_out)
             else:
                 wf = packed.get(spec.name, 'fwd') if packed is not None else pack_weight(weight, spec, 'fwd')
-                y = conv_forward(p_in, wf, bias, spec, relu_in, scale, shift, per_group, next_bn)
+                y = conv_forward(p_in, wf, bias, spec, fwd_relu, scale, shift, per_group, next_bn, relu_out)
             if next_bn:
                 y, part = y
         ctx.spec, ctx.relu_in, ctx.per_group, ctx.input_is_data, ctx.sync, ctx.has_bn = \
@@ -583,7 +596,7 @@ class BnConvAct(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy, *_unused):
         with label(ctx.spec.name + '/bwd'):
-            return BnConvAct._backward(ctx, dy) + (None, None, None)
+            return BnConvAct._backward(ctx, dy) + (None, None, None, None, None)
 
     @staticmethod
     def _backward(ctx, dy):
@@ -716,12 +729,13 @@ def _mm_for(packed, weight, spec, direction, read_size, write_size):
 
 
 def bn_conv_act(p_in, weight, bias, gamma, beta, spec, relu_in, per_group=None, input_is_data=False, sync=None, packed=None,
-                next_bn=None, pre_stats=None, producer_bias=None, bias_grad_by_consumer=False):
-    """-> y, or (y, statistics partials for the consuming BatchNorm3d) when next_bn is given."""
+                next_bn=None, pre_stats=None, producer_bias=None, bias_grad_by_consumer=False, relu_out=False, rectified_in=False):
+    """-> y, or (y, statistics partials for the consuming BatchNorm3d) when next_bn is given.
+    relu_out: y is stored rectified; rectified_in: p_in already is relu(p) (see BnConvAct)."""
     if per_group is None:
         per_group = p_in.shape[0]
     return BnConvAct.apply(p_in, weight, bias, gamma, beta, spec, relu_in, per_group, input_is_data, sync, packed, next_bn,
-                           pre_stats, producer_bias, bias_grad_by_consumer)
+                           pre_stats, producer_bias, bias_grad_by_consumer, relu_out, rectified_in)
 
 
 class GamElbo(torch.autograd.Function):
@@ -1248,12 +1262,12 @@ class MmPlan:
             self._dev[key] = (torch.from_numpy(self.tau).to(device), torch.from_numpy(self.dlt).to(device), torch.from_numpy(self.aidx).to(device))
         return self._dev[key]
 
-    def desc(self, N, relu_in, per_group):
+    def desc(self, N, relu_in, per_group, relu_out=False):
         d = _lib.MmDesc()
         for k in ('CI', 'CO', 'ID', 'IH', 'IW', 'OD', 'OH', 'OW', 'nq', 'PDT', 'PH', 'PW', 'PD', 'sdi', 'shi', 'swi', 'd0', 'LD', 'cc', 'sdo', 'sho',
                   'swo', 'tpc', 'slack', 'dbuf', 'PHB', 'hlo', 'hhi', 'waves'):
             setattr(d, k, int(getattr(self, k)))
-        d.N, d.relu_in, d.per_group = int(N), int(bool(relu_in)), int(per_group)
+        d.N, d.relu_in, d.per_group, d.relu_out = int(N), int(bool(relu_in)), int(per_group), int(bool(relu_out))
         for q in range(4):
             d.ks[q] = int(self.ks[q]) if q < self.nq else 0
             d.od0[q] = int(self.od0[q]) if q < self.nq else 0
@@ -1458,13 +1472,14 @@ def _mm_build(mode, S, pad, CI, CO, K, isz, osz, widx, force=None):
                   tau=tau.reshape(-1), dlt=dlt.reshape(-1), aidx=aidx, mode=mode)
 
 
-def conv_mm(x, plan: MmPlan, aimg, bias, relu_in, scale, shift, per_group, mask_src=None, next_bn=None):
-    """One vg_conv_mm launch: x [N][CI][...] -> y [N][CO][OD][OH][OW] (pre-activation); with next_bn also the statistics partials."""
+def conv_mm(x, plan: MmPlan, aimg, bias, relu_in, scale, shift, per_group, mask_src=None, next_bn=None, relu_out=False):
+    """One vg_conv_mm launch: x [N][CI][...] -> y [N][CO][OD][OH][OW] (pre-activation; rectified with relu_out); with next_bn also
+    the statistics partials."""
     lib = _lib.get_lib()
     N = x.shape[0]
     assert tuple(x.shape[1:]) == (plan.CI, plan.ID, plan.IH, plan.IW), (tuple(x.shape), plan.CI, plan.ID, plan.IH, plan.IW)
     tau, dlt, _ = plan.tables(x.device)
-    d = plan.desc(N, relu_in, per_group if scale is not None else 1)
+    d = plan.desc(N, relu_in, per_group if scale is not None else 1, relu_out)
     y = torch.empty((N, plan.CO, plan.OD, plan.OH, plan.OW), dtype=torch.float32, device=x.device)
     _chk(x); _chk(aimg)
     if next_bn:

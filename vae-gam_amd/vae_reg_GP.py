@@ -218,6 +218,10 @@ class VAE(nn.Module):
         self.recon_sums = None         # per-subject map sums left by reconstruct() for build_model_recons.mk_avg_maps
         self._graphs = {}
         self.last_gp_kl = None
+        # decoder hand-off: convt1..convt4 store their outputs rectified and convt2..convt5 are told so (ops.BnConvAct: relu_out /
+        # rectified_in) -- bit-identical results, prologue-free forwards of convt2 and convt4.  Off: everything stored pre-activation.
+        # (a captured step holds the launches of the setting it was captured with)
+        self.rectified_handoff = True
 
     # ------------------------------------------------------------------ gradient guard
     @property
@@ -359,15 +363,17 @@ class VAE(nn.Module):
         bca = ops.bn_conv_act
         # explicit hand-offs between neighbouring layers (ops.BnConvAct): convt2 / convt4 also accumulate the statistics of
         # bnt3 / bnt5 (st3, st5); the bias gradients of convt2 / convt4 come out of bnt3's / bnt5's backward
-        p = bca(p, self.convt1.weight, self.convt1.bias, self.bnt1.weight, self.bnt1.bias, dsp[0], True, per_group, False, s, self._packed)
+        r = bool(self.rectified_handoff)
+        p = bca(p, self.convt1.weight, self.convt1.bias, self.bnt1.weight, self.bnt1.bias, dsp[0], True, per_group, False, s, self._packed,
+                relu_out=r)                                                         # (its own input comes from fc8 and is raw)
         p, st3 = bca(p, self.convt2.weight, self.convt2.bias, None, None, dsp[1], True, per_group, False, s, self._packed,
-                     next_bn=per_group, bias_grad_by_consumer=True)
+                     next_bn=per_group, bias_grad_by_consumer=True, relu_out=r, rectified_in=r)
         p = bca(p, self.convt3.weight, self.convt3.bias, self.bnt3.weight, self.bnt3.bias, dsp[2], True, per_group, False, s, self._packed,
-                pre_stats=st3, producer_bias=self.convt2.bias)
+                pre_stats=st3, producer_bias=self.convt2.bias, relu_out=r, rectified_in=r)
         p, st5 = bca(p, self.convt4.weight, self.convt4.bias, None, None, dsp[3], True, per_group, False, s, self._packed,
-                     next_bn=per_group, bias_grad_by_consumer=True)
+                     next_bn=per_group, bias_grad_by_consumer=True, relu_out=r, rectified_in=r)
         p = bca(p, self.convt5.weight, self.convt5.bias, self.bnt5.weight, self.bnt5.bias, dsp[4], True, per_group, False, s, self._packed,
-                pre_stats=st5, producer_bias=self.convt4.bias, bias_grad_by_consumer=last_bias_by_consumer)
+                pre_stats=st5, producer_bias=self.convt4.bias, bias_grad_by_consumer=last_bias_by_consumer, rectified_in=r)
         return p.reshape(p.shape[0], self.img_dim)
 
     def decode(self, z):
