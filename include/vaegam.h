@@ -163,6 +163,11 @@ int vg_wgrad3d_plan(const vg_wgrad_desc* d, int32_t grouped, int32_t* out, int32
  * triples there (double[G][C][3]) so the caller can all-reduce them across ranks, and
  * vg_bn_finalize() turns reduced triples into scale/shift/mean/rstd. */
 int64_t vg_bn_ws_bytes(int32_t N, int32_t C, int64_t P, int32_t per_group);
+/* The launch plan of the streaming kernels behind vg_bn_stats, vg_bn_bwd_reduce, vg_bn_bwd_apply (and, with per_group = N,
+ * vg_channel_sum) for these arguments, from the planner the launchers use; nothing is launched.  out = {cp, ns}: cp chunks over
+ * the P positions of a sample times ns splits of a group's per_group samples = cp * ns blocks per (group, channel).  Arguments
+ * that vg_bn_ws_bytes answers -1 for return VG_ERR_ARG. */
+int vg_bn_plan(int32_t N, int32_t C, int64_t P, int32_t per_group, int32_t out[2]);
 int vg_bn_stats(const float* x, int32_t N, int32_t C, int64_t P, int32_t per_group, int32_t relu,
                 const float* gamma, const float* beta, float eps, void* ws, double* ext_sums,
                 float* scale, float* shift, float* mean, float* rstd, void* stream);

@@ -1,5 +1,6 @@
-"""Shared bodies of the kernel parity tests: each HIP operator against a plain PyTorch fp32
-reference of the same maths.  Run on CPU tensors through the host build of the kernels
+"""Shared bodies of the kernel parity tests: each HIP operator against a plain PyTorch reference of the same
+maths -- fp32 for the layer and chain cases, float64 where a case's docstring says so (the conv_mm, weight-gradient,
+FC and gain case matrices; the batch-norm kernels have theirs in bn_cases.py).  Run on CPU tensors through the host build of the kernels
 (tests/emu, index-arithmetic check) and on the GPU through libvaegam_hip.so (-m gpu)."""
 import numpy as np
 import torch

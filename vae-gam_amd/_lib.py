@@ -72,6 +72,7 @@ _PROTOS = {
     'vg_wgrad3d_plan': (ctypes.c_int, [ctypes.POINTER(WgradDesc), i32, ctypes.POINTER(i32), i32]),
     'vg_bn_tconv1_sums': (ctypes.c_int, [vp, vp, vp, vp, i32, i32, i32, vp, vp, i32, vp]),
     'vg_bn_ws_bytes': (i64, [i32, i32, i64, i32]),
+    'vg_bn_plan': (ctypes.c_int, [i32, i32, i64, i32, ctypes.POINTER(i32)]),
     'vg_bn_stats': (ctypes.c_int, [vp, i32, i32, i64, i32, i32, vp, vp, f32, vp, vp, vp, vp, vp, vp, vp]),
     'vg_bn_finalize': (ctypes.c_int, [vp, i32, i32, vp, vp, f32, vp, vp, vp, vp, vp]),
     'vg_bn_bwd_reduce': (ctypes.c_int, [vp, vp, i32, i32, i64, i32, i32, vp, vp, vp, vp, vp]),

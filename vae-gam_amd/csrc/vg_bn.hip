@@ -198,6 +198,16 @@ extern "C" int64_t vg_bn_ws_bytes(int32_t N, int32_t C, int64_t P, int32_t per_g
     return (int64_t)G * C * chunks * 2 * sizeof(double) + (int64_t)G * C * 3 * sizeof(double);
 }
 
+// the plan every launcher below takes for these arguments (vg_channel_sum: per_group = N); nothing is launched
+extern "C" int vg_bn_plan(int32_t N, int32_t C, int64_t P, int32_t per_group, int32_t out[2]) {
+    if (!out || N <= 0 || C <= 0 || P <= 0 || per_group <= 0 || N % per_group) {
+        vg_set_error("vg_bn_plan: bad arguments N=%d C=%d P=%lld per_group=%d", N, C, (long long)P, per_group); return VG_ERR_ARG;
+    }
+    const BnPlan pl = plan_for(P, per_group, C, N / per_group);
+    out[0] = pl.cp; out[1] = pl.ns;
+    return VG_OK;
+}
+
 static int bn_args_ok(const char* who, const void* x, int N, int C, long long P, int per_group) {
     if (!x || N <= 0 || C <= 0 || P <= 0 || per_group <= 0 || N % per_group) {
         vg_set_error("%s: bad arguments N=%d C=%d P=%lld per_group=%d", who, N, C, P, per_group); return VG_ERR_ARG;

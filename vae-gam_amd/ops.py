@@ -351,6 +351,14 @@ def _bn_ws(x, N, C, P, per_group):
     return torch.empty(nbytes // 8, dtype=torch.float64, device=x.device)
 
 
+def bn_plan(N, C, P, per_group):
+    """(cp, ns) of the batch-norm streaming launches for x [N][C][P] in groups of per_group samples (channel_sum: per_group = N),
+    from the library's own planner (vg_bn_plan): cp position chunks per sample, ns sample splits; nothing is launched."""
+    rec = (ctypes.c_int32 * 2)()
+    _lib.get_lib().call('vg_bn_plan', int(N), int(C), int(P), int(per_group), rec)
+    return int(rec[0]), int(rec[1])
+
+
 def bn_stats(x, gamma, beta, relu, per_group, sync=None, pre=None):
     """Batch statistics of relu?(x) per (group, channel) -> (scale, shift, mean, rstd), each [G*C].
     `sync(t)` (optional) all-reduces the raw [sum, sumsq, count] triples across data-parallel ranks.
