@@ -204,6 +204,9 @@ int vg_bn_bwd_apply(float* dxe_inout, const float* p, int32_t N, int32_t C, int6
  *           chsum[c] (+)= per-channel sum of dp (bias gradient of the layer that produced p; NULL = not wanted).
  * ws: vg_bn_tconv1_ws_bytes(N, C, ID, per_group) bytes.  Data-parallel callers all-reduce `sums` between the two calls. */
 int64_t vg_bn_tconv1_ws_bytes(int32_t N, int32_t C, int32_t ID, int32_t per_group);
+/* plan query of the pair: the LDS bytes a block stages for p [.][C][ID][IH][IW], or -1 (vg_last_error says why) where the pair refuses
+ * the geometry -- nothing is launched */
+int64_t vg_bn_tconv1_lds_bytes(int32_t C, int32_t ID, int32_t IH, int32_t IW);
 int vg_bn_bwd_reduce_tconv1(const float* dy, const float* w, const float* p, int32_t N, int32_t C, int32_t ID, int32_t IH, int32_t IW,
                             int32_t per_group, int32_t relu, const float* mean, const float* rstd, void* ws, double* sums, void* stream);
 int vg_bn_bwd_apply_tconv1(const float* dy, const float* w, const float* p, float* dp, int32_t N, int32_t C, int32_t ID, int32_t IH,
@@ -239,6 +242,24 @@ int vg_gam_elbo_bwd(const float* logits, const float* gain, const float* x, cons
                     const float* glm, const float* dist, const float* g_slp, const float* g_dist,
                     int32_t C, int32_t B, int64_t V, void* ws,
                     float* d_logits, float* d_gain, double* d_eps, float* d_total, int32_t total_accumulate, void* stream);
+
+/* Embedded grids: the network runs on a grid G = grid[0..2] that contains the data's native grid N = nat[0..2] at its low corner
+ * (nat[a] <= grid[a], row-major volumes, last axis fastest); V_N, V_G = the voxel counts.
+ *
+ * vg_embed_volumes: out[B][V_G] = x[B][V_N] zero-padded at the high end of each axis; every element of out is written by the one launch. */
+int vg_embed_volumes(const float* x, const int32_t* nat, const int32_t* grid, int32_t B, float* out, void* stream);
+/* vg_gam_elbo_fwd / _bwd with logits and d_logits [G=C+1][B][V_G] on the grid and x [B][V_N], eps [V_N], glm [C][V_N], d_eps [V_N],
+ * maps_out [G+1][B][V_N] on the native grid.  The padding takes no part: sum_log_prob, dist, d_gain and d_total sum native voxels only,
+ * d_logits is written as exact zeros there, and nothing of x / eps / glm outside the native tensors is addressed.  The per-voxel
+ * arithmetic and the two-stage reductions are those of the plain pair (the same kernels, instantiated with the index decode).
+ * ws: vg_gam_ws_bytes(C, B, V_G) bytes.  nat / grid: host arrays of three. */
+int vg_gam_elbo_fwd_embed(const float* logits, const float* gain, const float* x, const double* eps,
+                          const float* glm, int32_t C, int32_t B, const int32_t* nat, const int32_t* grid, void* ws,
+                          float* sum_log_prob, float* dist, float* maps_out, void* stream);
+int vg_gam_elbo_bwd_embed(const float* logits, const float* gain, const float* x, const double* eps,
+                          const float* glm, const float* dist, const float* g_slp, const float* g_dist,
+                          int32_t C, int32_t B, const int32_t* nat, const int32_t* grid, void* ws,
+                          float* d_logits, float* d_gain, double* d_eps, float* d_total, int32_t total_accumulate, void* stream);
 
 /* Batch-norm parameter gradients from vg_bn_bwd_reduce's per-(group, channel) sums:
  *   dgamma[c] (+)= sum_g sums[g][c][1],  dbeta[c] (+)= sum_g sums[g][c][0]   (accumulate != 0 adds into the .grad buffers;

@@ -78,6 +78,7 @@ _PROTOS = {
     'vg_bn_bwd_reduce': (ctypes.c_int, [vp, vp, i32, i32, i64, i32, i32, vp, vp, vp, vp, vp]),
     'vg_bn_bwd_apply': (ctypes.c_int, [vp, vp, i32, i32, i64, i32, i32, vp, vp, vp, vp, f64, vp, vp, vp, vp, i32, vp]),
     'vg_bn_tconv1_ws_bytes': (i64, [i32, i32, i32, i32]),
+    'vg_bn_tconv1_lds_bytes': (i64, [i32, i32, i32, i32]),
     'vg_bn_bwd_reduce_tconv1': (ctypes.c_int, [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp]),
     'vg_bn_bwd_apply_tconv1': (ctypes.c_int, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, f64, vp, vp, i32, vp]),
     'vg_bn_param_grad': (ctypes.c_int, [vp, i32, i32, vp, vp, i32, vp]),
@@ -95,6 +96,10 @@ _PROTOS = {
     'vg_gam_ws_bytes': (i64, [i32, i32, i64]),
     'vg_gam_elbo_fwd': (ctypes.c_int, [vp, vp, vp, vp, vp, i32, i32, i64, vp, vp, vp, vp, vp]),
     'vg_gam_elbo_bwd': (ctypes.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i64, vp, vp, vp, vp, vp, i32, vp]),
+    'vg_embed_volumes': (ctypes.c_int, [vp, ctypes.POINTER(i32), ctypes.POINTER(i32), i32, vp, vp]),
+    'vg_gam_elbo_fwd_embed': (ctypes.c_int, [vp, vp, vp, vp, vp, i32, i32, ctypes.POINTER(i32), ctypes.POINTER(i32), vp, vp, vp, vp, vp]),
+    'vg_gam_elbo_bwd_embed': (ctypes.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, ctypes.POINTER(i32), ctypes.POINTER(i32), vp, vp, vp, vp,
+                                             vp, i32, vp]),
     'vg_pack_weights': (ctypes.c_int, [vp, vp, vp, i32, i64, vp]),
     'vg_cholesky_f64': (ctypes.c_int, [vp, vp, i32, i32, vp]),
     'vg_conv_mm_stats_chunks': (i64, [ctypes.POINTER(MmDesc), i32]),

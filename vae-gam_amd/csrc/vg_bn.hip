@@ -492,6 +492,14 @@ extern "C" int64_t vg_bn_tconv1_ws_bytes(int32_t N, int32_t C, int32_t ID, int32
     return (int64_t)(N / per_group) * C * chunks * 2 * (int64_t)sizeof(double);
 }
 
+extern "C" int64_t vg_bn_tconv1_lds_bytes(int32_t C, int32_t ID, int32_t IH, int32_t IW) {
+    FtParams a;
+    size_t shmem = 0;
+    const float none = 0.f;                     // ft_setup only tests the pointers
+    if (ft_setup("vg_bn_tconv1_lds_bytes", &none, &none, &none, 1, C, ID, IH, IW, 1, &a, &shmem) != VG_OK) return -1;
+    return (int64_t)shmem;
+}
+
 extern "C" int vg_bn_bwd_reduce_tconv1(const float* dy, const float* w, const float* p, int32_t N, int32_t C, int32_t ID, int32_t IH,
                                        int32_t IW, int32_t per_group, int32_t relu, const float* mean, const float* rstd, void* ws,
                                        double* sums, void* stream) {

@@ -21,20 +21,68 @@ constexpr float LOG_SQRT_2PI = 0.91893853320467274178f;
 __device__ __forceinline__ float wsum(float v) { return vg_wave_sum(v); }     // (every lane gets the sum; callers use lane 0's)
 __device__ __forceinline__ float sigmoidf_(float z) { return 1.f / (1.f + expf(-z)); }
 
+// An embedded grid (include/vaegam.h): the logits live on the grid G, the data on the native grid N at G's low corner.  A grid voxel
+// index is split by two divisions by constants (gw, then gh) as multiply + shift with magic numbers prepared on the host:
+// m = floor(2^s / d) + 1 with s = 31 + ceil(log2 d) is exact for every index below 2^31 and fits 32 bits.
+struct GamGrid {
+    int nd, nh, nw, gd, gh, gw;
+    unsigned mw, mh;
+    int sw, sh;
+    long long Vn;
+};
+
+// grid voxel vg (< 2^31) -> is it a native voxel, and its index vn in the native tensor (meaningful only then)
+__device__ __forceinline__ bool grid_to_native(const GamGrid& e, long long vg, long long& vn) {
+    const unsigned v = (unsigned)vg;
+    const unsigned row = (unsigned)(((unsigned long long)v * e.mw) >> e.sw);
+    const unsigned w = v - row * (unsigned)e.gw;
+    const unsigned d = (unsigned)(((unsigned long long)row * e.mh) >> e.sh);
+    const unsigned h = row - d * (unsigned)e.gh;
+    vn = ((long long)d * e.nh + h) * e.nw + w;
+    return w < (unsigned)e.nw && h < (unsigned)e.nh && d < (unsigned)e.nd;
+}
+
+// out[b][vg] = x[b][vn] on native voxels, 0 in the padding.  grid (vchunks, B); consecutive lanes write consecutive floats and read
+// runs of nw consecutive floats
+__global__ void __launch_bounds__(GT)
+embed_k(const float* __restrict__ x, float* __restrict__ out, long long V, GamGrid e) {
+    const int b = blockIdx.y;
+    const long long v0 = (long long)blockIdx.x * GT * GV + threadIdx.x;
+#pragma unroll
+    for (int k = 0; k < GV; ++k) {
+        const long long v = v0 + (long long)k * GT;
+        if (v < V) {
+            long long n;
+            const bool nat = grid_to_native(e, v, n);
+            out[(size_t)b * V + v] = nat ? x[(size_t)b * e.Vn + n] : 0.f;
+        }
+    }
+}
+
 // grid (vchunks, B).  part_slp[b][chunk], part_d2[i][b][chunk]
+// EMB: V counts the voxels of the grid the logits are on, x / eps / glm / maps_out are on the native grid e.Vn; a voxel of the padding
+// is skipped like one behind the end.  Without EMB e is not read and the native index is the voxel index.
+template <bool EMB>
 __global__ void __launch_bounds__(GT)
 gam_fwd_k(const float* __restrict__ logits, const float* __restrict__ gain, const float* __restrict__ x,
           const double* __restrict__ eps, const float* __restrict__ glm, int C, int B, long long V,
-          float* __restrict__ part_slp, float* __restrict__ part_d2, float* __restrict__ maps_out) {
+          float* __restrict__ part_slp, float* __restrict__ part_d2, float* __restrict__ maps_out, GamGrid e) {
     __shared__ float red[GT / VG_WAVE][GMAXC + 1];
     const int chunk = blockIdx.x, b = blockIdx.y, chunks = gridDim.x;
     const int lane = threadIdx.x % VG_WAVE, wave = threadIdx.x / VG_WAVE;
     const long long v0 = (long long)chunk * GT * GV + threadIdx.x;
     float xrec[GV];
     bool ok[GV];
+    long long vn[GV];
 #pragma unroll
-    for (int k = 0; k < GV; ++k) { ok[k] = (v0 + (long long)k * GT) < V; xrec[k] = 0.f; }
-    const size_t BV = (size_t)B * V;
+    for (int k = 0; k < GV; ++k) {
+        vn[k] = v0 + (long long)k * GT;
+        ok[k] = vn[k] < V;
+        if (EMB) { const bool nat = grid_to_native(e, v0 + (long long)k * GT, vn[k]); ok[k] = ok[k] && nat; }
+        xrec[k] = 0.f;
+    }
+    const long long Vn = EMB ? e.Vn : V;
+    const size_t BV = (size_t)B * V, BVn = (size_t)B * Vn;
     // base map
 #pragma unroll
     for (int k = 0; k < GV; ++k)
@@ -42,7 +90,7 @@ gam_fwd_k(const float* __restrict__ logits, const float* __restrict__ gain, cons
             const long long v = v0 + (long long)k * GT;
             const float s = sigmoidf_(logits[(size_t)b * V + v]);
             xrec[k] = s;
-            if (maps_out) maps_out[(size_t)b * V + v] = s;
+            if (maps_out) maps_out[(size_t)b * Vn + vn[k]] = s;
         }
     for (int i = 1; i <= C; ++i) {
         const float gn = gain[(size_t)(i - 1) * B + b];
@@ -52,10 +100,10 @@ gam_fwd_k(const float* __restrict__ logits, const float* __restrict__ gain, cons
             if (ok[k]) {
                 const long long v = v0 + (long long)k * GT;
                 const float cons = gn * sigmoidf_(logits[(size_t)i * BV + (size_t)b * V + v]);
-                const float df = cons - glm[(size_t)(i - 1) * V + v];
+                const float df = cons - glm[(size_t)(i - 1) * Vn + vn[k]];
                 d2 = fmaf(df, df, d2);
                 xrec[k] += cons;
-                if (maps_out) maps_out[(size_t)i * BV + (size_t)b * V + v] = cons;
+                if (maps_out) maps_out[(size_t)i * BVn + (size_t)b * Vn + vn[k]] = cons;
             }
         d2 = wsum(d2);
         if (lane == 0) red[wave][i] = d2;
@@ -64,11 +112,11 @@ gam_fwd_k(const float* __restrict__ logits, const float* __restrict__ gain, cons
 #pragma unroll
     for (int k = 0; k < GV; ++k)
         if (ok[k]) {
-            const long long v = v0 + (long long)k * GT;
+            const long long v = vn[k];
             const float sg = (float)exp(-eps[v]);               // fp64 exp then cast, as :402
-            const float r = x[(size_t)b * V + v] - xrec[k];
+            const float r = x[(size_t)b * Vn + v] - xrec[k];
             lp += -(r * r) / (2.f * sg * sg) - logf(sg) - LOG_SQRT_2PI;   // Normal.log_prob
-            if (maps_out) maps_out[(size_t)(C + 1) * BV + (size_t)b * V + v] = xrec[k];
+            if (maps_out) maps_out[(size_t)(C + 1) * BVn + (size_t)b * Vn + v] = xrec[k];
         }
     lp = wsum(lp);
     if (lane == 0) red[wave][0] = lp;
@@ -101,22 +149,29 @@ gam_fwd_fold_k(const float* __restrict__ part_slp, const float* __restrict__ par
 // loop, fully unrolled); the per-(covariate, sample) sums of d gain leave the block as one partial per WAVE, so the sample loop has
 // no barrier at all (the first version re-read and re-evaluated all C+1 sigmoids and paid two __syncthreads per covariate and
 // sample: 228 us at batch 64 / 8 covariates against 60 us of HBM time).
-template <int CMAX>
+// EMB: as in gam_fwd_k; a thread on a voxel of the padding loads from clamped addresses like one behind the end, writes d_logits = 0
+// and adds nothing to any sum.  part_dsig is [bs][Vn].
+template <int CMAX, bool EMB>
 __global__ void __launch_bounds__(GT)
 gam_bwd_k(const float* __restrict__ logits, const float* __restrict__ gain, const float* __restrict__ x,
           const double* __restrict__ eps, const float* __restrict__ glm, const float* __restrict__ dist,
           const float* __restrict__ g_slp, const float* __restrict__ g_dist, int C, int B, long long V,
-          float* __restrict__ d_logits, float* __restrict__ part_dsig, float* __restrict__ part_dgain, float* __restrict__ part_tot) {
+          float* __restrict__ d_logits, float* __restrict__ part_dsig, float* __restrict__ part_dgain, float* __restrict__ part_tot,
+          GamGrid e) {
     const int vb = blockIdx.x, bs = blockIdx.y, BS = gridDim.y, nparts = gridDim.x * (GT / VG_WAVE);
     const int lane = threadIdx.x % VG_WAVE, wave = threadIdx.x / VG_WAVE;
     const long long v = (long long)vb * GT + threadIdx.x;
     const bool ok = v < V;
     const long long vc = ok ? v : V - 1;                               // clamped: loads stay unconditional, results are masked
+    long long nc = vc;                                                 // the voxel's index in the native tensors, clamped likewise
+    bool nat = ok;                                                     // a voxel that counts
+    if (EMB) { nat = grid_to_native(e, vc, nc) && ok; if (!nat) nc = 0; }
+    const long long Vn = EMB ? e.Vn : V;
     const size_t BV = (size_t)B * V;
-    const float sg = (float)exp(-eps[vc]), inv_var = 1.f / (sg * sg);
+    const float sg = (float)exp(-eps[nc]), inv_var = 1.f / (sg * sg);
     float glm_v[CMAX];
 #pragma unroll
-    for (int i = 0; i < CMAX; ++i) glm_v[i] = i < C ? glm[(size_t)i * V + vc] : 0.f;
+    for (int i = 0; i < CMAX; ++i) glm_v[i] = i < C ? glm[(size_t)i * Vn + nc] : 0.f;
     float dsig = 0.f, tot = 0.f;                                       // tot: sum of every d_logits element this thread writes
     for (int b = bs; b < B; b += BS) {
         const size_t row = (size_t)b * V + vc;
@@ -127,7 +182,7 @@ gam_bwd_k(const float* __restrict__ logits, const float* __restrict__ gain, cons
             sgm[i + 1] = i < C ? logits[(size_t)(i + 1) * BV + row] : 0.f;
             gn[i] = i < C ? gain[(size_t)i * B + b] : 0.f;
         }
-        const float xv = x[row], gs = g_slp[b];
+        const float xv = x[(size_t)b * Vn + nc], gs = g_slp[b];
 #pragma unroll
         for (int i = 0; i <= CMAX; ++i) sgm[i] = sigmoidf_(sgm[i]);
         float xr = sgm[0];
@@ -135,11 +190,11 @@ gam_bwd_k(const float* __restrict__ logits, const float* __restrict__ gain, cons
         for (int i = 0; i < CMAX; ++i) xr += gn[i] * sgm[i + 1];         // (gn = 0 beyond C)
         const float r = xv - xr;
         const float dxr = gs * r * inv_var;                            // d slp / d x_rec = r / sigma^2
-        if (ok) {
+        if (nat) {
             dsig += gs * (r * r * inv_var / sg - 1.f / sg);            // d slp / d sigma
             const float dl = dxr * sgm[0] * (1.f - sgm[0]);
             d_logits[row] = dl; tot += dl;
-        }
+        } else if (EMB && ok) d_logits[row] = 0.f;
 #pragma unroll
         for (int i = 0; i < CMAX; ++i) {
             if (i < C) {                                               // wave-uniform
@@ -148,13 +203,14 @@ gam_bwd_k(const float* __restrict__ logits, const float* __restrict__ gain, cons
                 float dcons = dxr;
                 if (dd > 0.f) dcons += g_dist[(size_t)i * B + b] * (gn[i] * s_ - glm_v[i]) / dd;
                 const float dl = dcons * gn[i] * s_ * (1.f - s_);
-                if (ok) { d_logits[(size_t)(i + 1) * BV + row] = dl; tot += dl; }
-                const float dg = wsum(ok ? dcons * s_ : 0.f);
+                if (nat) { d_logits[(size_t)(i + 1) * BV + row] = dl; tot += dl; }
+                else if (EMB && ok) d_logits[(size_t)(i + 1) * BV + row] = 0.f;
+                const float dg = wsum(nat ? dcons * s_ : 0.f);
                 if (lane == 0) part_dgain[((size_t)i * B + b) * nparts + vb * (GT / VG_WAVE) + wave] = dg;
             }
         }
     }
-    if (ok) part_dsig[(size_t)bs * V + v] = dsig;
+    if (nat) part_dsig[(size_t)bs * Vn + nc] = dsig;
     if (part_tot) {
         tot = wsum(tot);
         if (lane == 0) part_tot[((size_t)bs * gridDim.x + vb) * (GT / VG_WAVE) + wave] = tot;
@@ -390,9 +446,81 @@ extern "C" int64_t vg_gam_ws_bytes(int32_t C, int32_t B, int64_t V) {
     return fwd > bwd ? fwd : bwd;
 }
 
+namespace {
+
+void grid_magic(unsigned d, unsigned& m, int& s) {
+    int c = 0;
+    while ((1u << c) < d) ++c;
+    s = 31 + c;
+    m = (unsigned)(((1ull << s) / d) + 1);
+}
+
+// -> V_G, or -1: nat must fit into grid and the grid's voxel indices (plus a block's overhang) into 31 bits
+long long make_grid(const int32_t* nat, const int32_t* grid, GamGrid& e) {
+    if (!nat || !grid) return -1;
+    for (int a = 0; a < 3; ++a) if (nat[a] < 1 || grid[a] < nat[a]) return -1;
+    const long long Vg = (long long)grid[0] * grid[1] * grid[2];
+    if (Vg > 0x7fffffffLL - 2 * GT * GV) return -1;
+    e.nd = nat[0]; e.nh = nat[1]; e.nw = nat[2]; e.gd = grid[0]; e.gh = grid[1]; e.gw = grid[2];
+    grid_magic((unsigned)e.gw, e.mw, e.sw);
+    grid_magic((unsigned)e.gh, e.mh, e.sh);
+    e.Vn = (long long)nat[0] * nat[1] * nat[2];
+    return Vg;
+}
+
+int gam_fwd(const float* logits, const float* gain, const float* x, const double* eps, const float* glm, int32_t C, int32_t B, int64_t V,
+            const GamGrid* e, void* ws, float* sum_log_prob, float* dist, float* maps_out, void* stream);
+int gam_bwd(const float* logits, const float* gain, const float* x, const double* eps, const float* glm, const float* dist,
+            const float* g_slp, const float* g_dist, int32_t C, int32_t B, int64_t V, const GamGrid* e, void* ws,
+            float* d_logits, float* d_gain, double* d_eps, float* d_total, int32_t total_accumulate, void* stream);
+
+}  // namespace
+
+extern "C" int vg_embed_volumes(const float* x, const int32_t* nat, const int32_t* grid, int32_t B, float* out, void* stream) {
+    GamGrid e;
+    const long long V = make_grid(nat, grid, e);
+    if (!x || !out || V < 0 || B <= 0 || B > 65535) { vg_set_error("vg_embed_volumes: bad arguments B=%d", B); return VG_ERR_ARG; }
+    vg_launch(embed_k, dim3(fwd_chunks(V), B), dim3(GT), 0, (hipStream_t)stream, x, out, V, e);
+    return vg_check_launch("embed_volumes");
+}
+
 extern "C" int vg_gam_elbo_fwd(const float* logits, const float* gain, const float* x, const double* eps,
                                const float* glm, int32_t C, int32_t B, int64_t V, void* ws,
                                float* sum_log_prob, float* dist, float* maps_out, void* stream) {
+    return gam_fwd(logits, gain, x, eps, glm, C, B, V, nullptr, ws, sum_log_prob, dist, maps_out, stream);
+}
+
+extern "C" int vg_gam_elbo_fwd_embed(const float* logits, const float* gain, const float* x, const double* eps,
+                                     const float* glm, int32_t C, int32_t B, const int32_t* nat, const int32_t* grid, void* ws,
+                                     float* sum_log_prob, float* dist, float* maps_out, void* stream) {
+    GamGrid e;
+    const long long V = make_grid(nat, grid, e);
+    if (V < 0) { vg_set_error("vg_gam_elbo_fwd_embed: the native grid must fit into a grid of less than 2^31 voxels"); return VG_ERR_ARG; }
+    return gam_fwd(logits, gain, x, eps, glm, C, B, V, &e, ws, sum_log_prob, dist, maps_out, stream);
+}
+
+extern "C" int vg_gam_elbo_bwd(const float* logits, const float* gain, const float* x, const double* eps,
+                               const float* glm, const float* dist, const float* g_slp, const float* g_dist,
+                               int32_t C, int32_t B, int64_t V, void* ws,
+                               float* d_logits, float* d_gain, double* d_eps, float* d_total, int32_t total_accumulate, void* stream) {
+    return gam_bwd(logits, gain, x, eps, glm, dist, g_slp, g_dist, C, B, V, nullptr, ws, d_logits, d_gain, d_eps, d_total, total_accumulate, stream);
+}
+
+extern "C" int vg_gam_elbo_bwd_embed(const float* logits, const float* gain, const float* x, const double* eps,
+                                     const float* glm, const float* dist, const float* g_slp, const float* g_dist,
+                                     int32_t C, int32_t B, const int32_t* nat, const int32_t* grid, void* ws,
+                                     float* d_logits, float* d_gain, double* d_eps, float* d_total, int32_t total_accumulate, void* stream) {
+    GamGrid e;
+    const long long V = make_grid(nat, grid, e);
+    if (V < 0) { vg_set_error("vg_gam_elbo_bwd_embed: the native grid must fit into a grid of less than 2^31 voxels"); return VG_ERR_ARG; }
+    return gam_bwd(logits, gain, x, eps, glm, dist, g_slp, g_dist, C, B, V, &e, ws, d_logits, d_gain, d_eps, d_total, total_accumulate, stream);
+}
+
+namespace {
+
+// V: voxels of the tensor the logits are on; emb: the embedded grid, or nullptr (everything on one grid)
+int gam_fwd(const float* logits, const float* gain, const float* x, const double* eps, const float* glm, int32_t C, int32_t B, int64_t V,
+            const GamGrid* emb, void* ws, float* sum_log_prob, float* dist, float* maps_out, void* stream) {
     if (!logits || !x || !eps || !ws || !sum_log_prob || (C > 0 && (!gain || !glm || !dist)) || C < 0 || C > GMAXC || B <= 0 ||
         B > 65535 || V <= 0) {
         vg_set_error("vg_gam_elbo_fwd: bad arguments C=%d B=%d V=%lld", C, B, (long long)V); return VG_ERR_ARG;
@@ -401,7 +529,12 @@ extern "C" int vg_gam_elbo_fwd(const float* logits, const float* gain, const flo
     const int chunks = fwd_chunks(V);
     float* part_slp = (float*)ws;
     float* part_d2 = part_slp + (size_t)B * chunks;
-    vg_launch(gam_fwd_k, dim3(chunks, B), dim3(GT), 0, s, logits, gain, x, eps, glm, (int)C, (int)B, (long long)V, part_slp, part_d2, maps_out);
+    if (emb)
+        vg_launch(gam_fwd_k<true>, dim3(chunks, B), dim3(GT), 0, s, logits, gain, x, eps, glm, (int)C, (int)B, (long long)V, part_slp, part_d2,
+                  maps_out, *emb);
+    else
+        vg_launch(gam_fwd_k<false>, dim3(chunks, B), dim3(GT), 0, s, logits, gain, x, eps, glm, (int)C, (int)B, (long long)V, part_slp, part_d2,
+                  maps_out, GamGrid{});
     int rc = vg_check_launch("gam_fwd");
     if (rc) return rc;
     vg_launch(gam_fwd_fold_k, dim3((C + 1) * B), dim3(64), 0, s, (const float*)part_slp, (const float*)part_d2,
@@ -409,10 +542,9 @@ extern "C" int vg_gam_elbo_fwd(const float* logits, const float* gain, const flo
     return vg_check_launch("gam_fwd_fold");
 }
 
-extern "C" int vg_gam_elbo_bwd(const float* logits, const float* gain, const float* x, const double* eps,
-                               const float* glm, const float* dist, const float* g_slp, const float* g_dist,
-                               int32_t C, int32_t B, int64_t V, void* ws,
-                               float* d_logits, float* d_gain, double* d_eps, float* d_total, int32_t total_accumulate, void* stream) {
+int gam_bwd(const float* logits, const float* gain, const float* x, const double* eps, const float* glm, const float* dist,
+            const float* g_slp, const float* g_dist, int32_t C, int32_t B, int64_t V, const GamGrid* emb, void* ws,
+            float* d_logits, float* d_gain, double* d_eps, float* d_total, int32_t total_accumulate, void* stream) {
     if (!logits || !x || !eps || !ws || !g_slp || !d_logits || !d_eps || (C > 0 && (!gain || !glm || !dist || !g_dist || !d_gain)) ||
         C < 0 || C > GMAXC || B <= 0 || V <= 0) {
         vg_set_error("vg_gam_elbo_bwd: bad arguments C=%d B=%d V=%lld", C, B, (long long)V); return VG_ERR_ARG;
@@ -422,20 +554,22 @@ extern "C" int vg_gam_elbo_bwd(const float* logits, const float* gain, const flo
     float* part_dsig = (float*)ws;
     float* part_dgain = part_dsig + (size_t)BS * V;
     float* part_tot = d_total ? part_dgain + (size_t)C * B * bwd_gain_parts(V) : nullptr;
-    if (C <= 8)
-        vg_launch(gam_bwd_k<8>, dim3(vblocks, BS), dim3(GT), 0, s, logits, gain, x, eps, glm, dist, g_slp, g_dist, (int)C, (int)B,
-                  (long long)V, d_logits, part_dsig, part_dgain, part_tot);
-    else if (C <= 16)
-        vg_launch(gam_bwd_k<16>, dim3(vblocks, BS), dim3(GT), 0, s, logits, gain, x, eps, glm, dist, g_slp, g_dist, (int)C, (int)B,
-                  (long long)V, d_logits, part_dsig, part_dgain, part_tot);
+    const GamGrid e = emb ? *emb : GamGrid{};
+    const long long Vn = emb ? emb->Vn : (long long)V;                   // voxels of x / eps / d_eps
+#define VG_GAM_BWD(CMAX, EMB)                                                                                                     \
+    vg_launch(gam_bwd_k<CMAX, EMB>, dim3(vblocks, BS), dim3(GT), 0, s, logits, gain, x, eps, glm, dist, g_slp, g_dist, (int)C, (int)B, \
+              (long long)V, d_logits, part_dsig, part_dgain, part_tot, e)
+    if (C <= 8) { if (emb) VG_GAM_BWD(8, true); else VG_GAM_BWD(8, false); }
+    else if (C <= 16) { if (emb) VG_GAM_BWD(16, true); else VG_GAM_BWD(16, false); }
     else { vg_set_error("vg_gam_elbo_bwd: more than 16 covariates"); return VG_ERR_UNSUPPORTED; }
+#undef VG_GAM_BWD
     int rc = vg_check_launch("gam_bwd");
     if (rc) return rc;
     if (C > 0) {
         vg_launch(gam_bwd_fold_gain_k, dim3(C * B), dim3(64), 0, s, (const float*)part_dgain, (int)(C * B), bwd_gain_parts(V), d_gain);
         if ((rc = vg_check_launch("gam_bwd_fold_gain"))) return rc;
     }
-    vg_launch(gam_bwd_fold_eps_k, dim3((unsigned)((V + 255) / 256)), dim3(256), 0, s, (const float*)part_dsig, eps, BS, (long long)V, d_eps);
+    vg_launch(gam_bwd_fold_eps_k, dim3((unsigned)((Vn + 255) / 256)), dim3(256), 0, s, (const float*)part_dsig, eps, BS, Vn, d_eps);
     if ((rc = vg_check_launch("gam_bwd_fold_eps"))) return rc;
     if (d_total) {
         vg_launch(gam_bwd_fold_total_k, dim3(1), dim3(256), 0, s, (const float*)part_tot, BS * bwd_gain_parts(V), (int)total_accumulate, d_total);
@@ -443,6 +577,8 @@ extern "C" int vg_gam_elbo_bwd(const float* logits, const float* gain, const flo
     }
     return VG_OK;
 }
+
+}  // namespace
 
 extern "C" int vg_adam_advance(double* state, double lr, double b1, double b2, void* stream) {
     if (!state || !(lr > 0) || !(b1 >= 0 && b1 < 1) || !(b2 >= 0 && b2 < 1)) { vg_set_error("vg_adam_advance: bad arguments"); return VG_ERR_ARG; }

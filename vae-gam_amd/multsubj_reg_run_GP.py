@@ -57,7 +57,25 @@ def build_parser():
     parser.add_argument('--hip_graph', type=str2bool, nargs='?', const=True, default=False,
                         help='(extension) Capture the train step into a hipGraph once per batch shape and replay it; where capture is '
                              'refused the step runs as eager launches and says so.')
+    parser.add_argument('--img_shape', type=int, nargs=3, metavar=('X', 'Y', 'Z'), default=list(vae_reg.IMG_SHAPE),
+                        help='(extension) Spatial shape of the volumes (default: the reference\'s 41 49 35).  Any grid with axes >= 19; one '
+                             'whose axes are not all = 2 (mod 4) is zero-padded by up to 3 voxels per axis inside the network, while the '
+                             'loss and every exported map stay on the grid given here.  The padded grid X x H x W must have W <= 130 and '
+                             'H*W <= 7667 (91 109 91 -> 94x110x94 is refused).')
     return parser
+
+
+def check_img_shape(img_shape, loaders):
+    """ValueError if the first subject file of the training set does not hold volumes of --img_shape (read from the file's header)."""
+    loader = loaders.get('UnShuffled_train')
+    df = getattr(getattr(loader, 'dataset', None), 'df', None)
+    if df is None or not len(df):
+        return
+    path = df.iloc[0, 3]
+    found = tuple(int(v) for v in data._probe_volume_file(path)['shape'][:3])
+    if found != tuple(img_shape):
+        raise ValueError('--img_shape is %s but the volumes of %s have the spatial shape %s'
+                         % ('x'.join(map(str, img_shape)), path, 'x'.join(map(str, found))))
 
 
 def main(argv=None):
@@ -91,11 +109,12 @@ def main(argv=None):
         full_loaders = data.setup_data_loaders(batch_size=args.batch_size, train_csv=args.train_csv, test_csv=args.test_csv,
                                                prefetch_device='cuda' if (dp is None and torch.cuda.is_available()) else None)
     loaders_dict = full_loaders if dp is None else dp.shard_loaders(full_loaders, args.batch_size, args.seed)
+    check_img_shape(args.img_shape, full_loaders)
     model = vae_reg.VAE(num_inducing_pts=args.num_inducing_pts, gp_kl_scale=args.gp_kl_scale,
                         glm_reg_scale=args.glm_reg_scale, glm_maps=args.glm_maps, save_dir=args.save_dir,
                         csv_files=[args.train_csv, args.test_csv], neural_covariates=args.neural_covariates,
                         data_parallel=dp, dp_gain=os.environ.get('VG_DP_GAIN', 'global'), gp_jitter=args.gp_jitter,
-                        max_grad_norm=args.max_grad_norm, skip_nonfinite=args.skip_nonfinite)
+                        max_grad_norm=args.max_grad_norm, skip_nonfinite=args.skip_nonfinite, img_shape=tuple(args.img_shape))
     model.use_hip_graph = bool(args.hip_graph)
     if args.from_ckpt:
         assert os.path.exists(args.ckpt_path), 'Oops, looks like ckpt file given does NOT exist!'

@@ -746,6 +746,62 @@ def bn_conv_act(p_in, weight, bias, gamma, beta, spec, relu_in, per_group=None, 
                            pre_stats, producer_bias, bias_grad_by_consumer, relu_out, rectified_in)
 
 
+def _i3(v):
+    v = tuple(int(a) for a in v)
+    assert len(v) == 3
+    return (ctypes.c_int32 * 3)(*v)
+
+
+def _gam_forward(ctx, logits, gain, x, eps, glm, logits_bias, nat=None, grid=None):
+    """forward of GamElbo (nat is None: everything on one grid) and GamElboEmbed"""
+    lib = _lib.get_lib()
+    G, B, V = logits.shape
+    C = G - 1
+    logits = _chk(logits.contiguous()); gain = _chk(gain.contiguous()); x = _chk(x.contiguous())
+    eps = _chk(eps.contiguous(), torch.float64); glm = _chk(glm.contiguous())
+    ws = torch.empty(lib.size('vg_gam_ws_bytes', C, B, V) // 4 + 1, dtype=torch.float32, device=x.device)
+    slp = torch.empty(B, dtype=torch.float32, device=x.device)
+    dist = torch.empty((C, B), dtype=torch.float32, device=x.device)
+    if nat is None:
+        _call(x, 'vg_gam_elbo_fwd', _p(logits), _p(gain), _p(x), _p(eps), _p(glm), C, B, V, _p(ws), _p(slp), _p(dist),
+                 None)
+    else:
+        Vn = nat[0] * nat[1] * nat[2]
+        assert V == grid[0] * grid[1] * grid[2] and x.shape == (B, Vn) and eps.shape == (Vn,) and (C == 0 or glm.shape == (C, Vn))
+        _call(x, 'vg_gam_elbo_fwd_embed', _p(logits), _p(gain), _p(x), _p(eps), _p(glm), C, B, _i3(nat), _i3(grid), _p(ws), _p(slp),
+                 _p(dist), None)
+    ctx.save_for_backward(logits, gain, x, eps, glm, dist)
+    ctx.logits_bias, ctx.nat, ctx.grid = logits_bias, nat, grid
+    return slp, dist
+
+
+def _gam_backward(ctx, g_slp, g_dist):
+    """-> d_logits, d_gain, d_eps; sum(d_logits) is added into ctx.logits_bias.grad"""
+    lib = _lib.get_lib()
+    logits, gain, x, eps, glm, dist = ctx.saved_tensors
+    tot = None
+    if ctx.logits_bias is not None:
+        pb = ctx.logits_bias
+        assert pb.numel() == 1
+        if pb.grad is None:
+            raise RuntimeError('GamElbo: logits_bias.grad is not bound (see bn_conv_act: the bias gradient is added into the caller\'s buffer)')
+        tot = pb.grad
+    G, B, V = logits.shape
+    C = G - 1
+    g_slp = _chk(g_slp.contiguous()); g_dist = _chk(g_dist.contiguous())
+    ws = torch.empty(lib.size('vg_gam_ws_bytes', C, B, V) // 4 + 1, dtype=torch.float32, device=x.device)
+    d_logits = torch.empty_like(logits)
+    d_gain = torch.empty_like(gain)
+    d_eps = torch.empty_like(eps)
+    if ctx.nat is None:
+        _call(x, 'vg_gam_elbo_bwd', _p(logits), _p(gain), _p(x), _p(eps), _p(glm), _p(dist), _p(g_slp), _p(g_dist),
+                 C, B, V, _p(ws), _p(d_logits), _p(d_gain), _p(d_eps), _p(tot), 1)
+    else:
+        _call(x, 'vg_gam_elbo_bwd_embed', _p(logits), _p(gain), _p(x), _p(eps), _p(glm), _p(dist), _p(g_slp), _p(g_dist),
+                 C, B, _i3(ctx.nat), _i3(ctx.grid), _p(ws), _p(d_logits), _p(d_gain), _p(d_eps), _p(tot), 1)
+    return d_logits, d_gain, d_eps
+
+
 class GamElbo(torch.autograd.Function):
     """(logits[G,B,V], gain[C,B], x[B,V], eps[V] f64, glm[C,V]) -> (sum_log_prob[B], dist[C,B]).
     `logits_bias` (optional Parameter of one element): the bias of the one-output-channel layer that produced `logits`; the backward
@@ -753,41 +809,40 @@ class GamElbo(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, logits, gain, x, eps, glm, logits_bias=None):
-        lib = _lib.get_lib()
-        G, B, V = logits.shape
-        C = G - 1
-        logits = _chk(logits.contiguous()); gain = _chk(gain.contiguous()); x = _chk(x.contiguous())
-        eps = _chk(eps.contiguous(), torch.float64); glm = _chk(glm.contiguous())
-        ws = torch.empty(lib.size('vg_gam_ws_bytes', C, B, V) // 4 + 1, dtype=torch.float32, device=x.device)
-        slp = torch.empty(B, dtype=torch.float32, device=x.device)
-        dist = torch.empty((C, B), dtype=torch.float32, device=x.device)
-        _call(x, 'vg_gam_elbo_fwd', _p(logits), _p(gain), _p(x), _p(eps), _p(glm), C, B, V, _p(ws), _p(slp), _p(dist),
-                 None)
-        ctx.save_for_backward(logits, gain, x, eps, glm, dist)
-        ctx.logits_bias = logits_bias
-        return slp, dist
+        return _gam_forward(ctx, logits, gain, x, eps, glm, logits_bias)
 
     @staticmethod
     def backward(ctx, g_slp, g_dist):
-        lib = _lib.get_lib()
-        logits, gain, x, eps, glm, dist = ctx.saved_tensors
-        tot = None
-        if ctx.logits_bias is not None:
-            pb = ctx.logits_bias
-            assert pb.numel() == 1
-            if pb.grad is None:
-                raise RuntimeError('GamElbo: logits_bias.grad is not bound (see bn_conv_act: the bias gradient is added into the caller\'s buffer)')
-            tot = pb.grad
-        G, B, V = logits.shape
-        C = G - 1
-        g_slp = _chk(g_slp.contiguous()); g_dist = _chk(g_dist.contiguous())
-        ws = torch.empty(lib.size('vg_gam_ws_bytes', C, B, V) // 4 + 1, dtype=torch.float32, device=x.device)
-        d_logits = torch.empty_like(logits)
-        d_gain = torch.empty_like(gain)
-        d_eps = torch.empty_like(eps)
-        _call(x, 'vg_gam_elbo_bwd', _p(logits), _p(gain), _p(x), _p(eps), _p(glm), _p(dist), _p(g_slp), _p(g_dist),
-                 C, B, V, _p(ws), _p(d_logits), _p(d_gain), _p(d_eps), _p(tot), 1)
+        d_logits, d_gain, d_eps = _gam_backward(ctx, g_slp, g_dist)
         return d_logits, d_gain, None, d_eps, None, None
+
+
+class GamElboEmbed(torch.autograd.Function):
+    """GamElbo for a network that runs on a grid larger than the data's (schema.NetGeometry.pad != 0): logits[G,B,V_grid] on the
+    grid, x[B,V_nat], eps[V_nat] f64, glm[C,V_nat] on the native grid `nat` at the low corner of `grid`
+    -> (sum_log_prob[B], dist[C,B]) over native voxels only.  The gradient of the logits is exactly zero in the padding.
+    `logits_bias`: as in GamElbo."""
+
+    @staticmethod
+    def forward(ctx, logits, gain, x, eps, glm, nat, grid, logits_bias=None):
+        return _gam_forward(ctx, logits, gain, x, eps, glm, logits_bias, tuple(int(a) for a in nat), tuple(int(a) for a in grid))
+
+    @staticmethod
+    def backward(ctx, g_slp, g_dist):
+        d_logits, d_gain, d_eps = _gam_backward(ctx, g_slp, g_dist)
+        return d_logits, d_gain, None, d_eps, None, None, None, None
+
+
+def embed_volumes(x, nat, grid):
+    """x (B, *nat) or (B, V_nat) -> (B, *grid): zero-padded at the high end of each axis, one launch that writes every element
+    (vg_embed_volumes).  No gradient: the data has none."""
+    nat = tuple(int(a) for a in nat); grid = tuple(int(a) for a in grid)
+    B = x.shape[0]
+    x = _chk(x.detach().reshape(B, -1).contiguous())
+    assert x.shape[1] == nat[0] * nat[1] * nat[2], (x.shape, nat)
+    out = torch.empty((B,) + grid, dtype=torch.float32, device=x.device)
+    _call(x, 'vg_embed_volumes', _p(x), _i3(nat), _i3(grid), B, _p(out))
+    return out
 
 
 class LatentSample(torch.autograd.Function):
@@ -1018,18 +1073,24 @@ def linear_act(layer, x, relu, relu_in=False):
     return LinearAct.apply(x, layer.weight, layer.bias, relu, relu_in)
 
 
-def gam_maps(logits, gain, x, eps, glm):
-    """Reconstruction path (vae_reg_GP.py:331,391-392): the C+2 maps [base, cons_1..C, full_rec] as [C+2,B,V]."""
+def gam_maps(logits, gain, x, eps, glm, nat=None, grid=None):
+    """Reconstruction path (vae_reg_GP.py:331,391-392): the C+2 maps [base, cons_1..C, full_rec] as [C+2,B,V].
+    With nat / grid (see GamElboEmbed) the logits are on the grid and the maps come out on the native grid: V = V_nat."""
     lib = _lib.get_lib()
     G, B, V = logits.shape
     C = G - 1
+    Vn = V if nat is None else int(nat[0]) * int(nat[1]) * int(nat[2])
     ws = torch.empty(lib.size('vg_gam_ws_bytes', C, B, V) // 4 + 1, dtype=torch.float32, device=x.device)
     slp = torch.empty(B, dtype=torch.float32, device=x.device)
     dist = torch.empty((max(C, 1), B), dtype=torch.float32, device=x.device)
-    maps = torch.empty((G + 1, B, V), dtype=torch.float32, device=x.device)
-    _call(x, 'vg_gam_elbo_fwd', _p(_chk(logits.contiguous())), _p(_chk(gain.contiguous())), _p(_chk(x.contiguous())),
-             _p(_chk(eps.contiguous(), torch.float64)), _p(_chk(glm.contiguous())), C, B, V, _p(ws), _p(slp), _p(dist),
-             _p(maps))
+    maps = torch.empty((G + 1, B, Vn), dtype=torch.float32, device=x.device)
+    ptrs = (_p(_chk(logits.contiguous())), _p(_chk(gain.contiguous())), _p(_chk(x.contiguous())),
+            _p(_chk(eps.contiguous(), torch.float64)), _p(_chk(glm.contiguous())))
+    if nat is None:
+        _call(x, 'vg_gam_elbo_fwd', *ptrs, C, B, V, _p(ws), _p(slp), _p(dist), _p(maps))
+    else:
+        assert V == int(grid[0]) * int(grid[1]) * int(grid[2]) and x.shape == (B, Vn)
+        _call(x, 'vg_gam_elbo_fwd_embed', *ptrs, C, B, _i3(nat), _i3(grid), _p(ws), _p(slp), _p(dist), _p(maps))
     return maps
 
 

@@ -28,14 +28,23 @@ _GLYPH = np.array([[0, 0, 0, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0],
 
 def large3_signal(img_shape=(41, 49, 35), intensity=1000.0):
     """Control-signal volume: glyph rotated -90 deg, broadcast to 10 slices, at [15:25, 34:47, 9:22]
-    (x2 per axis at 82x98x70), amplitude intensity/3284.5."""
-    scale = img_shape[0] // 41
+    (x2 per axis at 82x98x70; on any other grid the block sits at the same fractions of each axis, the glyph resampled to the
+    nearest voxel), amplitude intensity/3284.5."""
     glyph = np.rot90(_GLYPH, k=-1)                       # ndimage.rotate(sig, -90) on a square binary image
     sig = np.broadcast_to(glyph, (10, 13, 13)).copy()
-    if scale > 1:
-        sig = sig.repeat(scale, 0).repeat(scale, 1).repeat(scale, 2)
     out = np.zeros(img_shape)
-    out[15 * scale:25 * scale, 34 * scale:47 * scale, 9 * scale:22 * scale] += sig
+    if tuple(img_shape) in ((41, 49, 35), (82, 98, 70)):
+        scale = img_shape[0] // 41
+        if scale > 1:
+            sig = sig.repeat(scale, 0).repeat(scale, 1).repeat(scale, 2)
+        out[15 * scale:25 * scale, 34 * scale:47 * scale, 9 * scale:22 * scale] += sig
+    else:
+        sl, ix = [], []
+        for a, (lo, hi, n) in enumerate(((15, 25, 41), (34, 47, 49), (9, 22, 35))):
+            l = int(round(lo * img_shape[a] / n)); h = max(l + 1, int(round(hi * img_shape[a] / n)))
+            sl.append(slice(l, h))
+            ix.append(np.minimum(((np.arange(h - l) + 0.5) * (hi - lo) / (h - l)).astype(np.int64), hi - lo - 1))
+        out[tuple(sl)] += sig[np.ix_(*ix)]
     return out * (intensity / 3284.5)
 
 

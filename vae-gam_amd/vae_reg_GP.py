@@ -99,7 +99,10 @@ class VAE(nn.Module):
                  neural_covariates=True, *, img_shape=IMG_SHAPE, xu_ranges=None, tensorboard=False,
                  data_parallel=None, gp_jitter=0.0, dp_gain='global', max_grad_norm=None, skip_nonfinite=False):
         """Arguments up to `neural_covariates` are the reference's (vae_reg_GP.py:36-37).
-        Keyword-only extensions: `img_shape` (41x49x35 or 82x98x70), `xu_ranges` (inducing-point
+        Keyword-only extensions: `img_shape` (the data's grid: 41x49x35, 82x98x70 and grids with every axis = 2 (mod 4) run as they
+        are, any other with axes >= 19 is embedded into the next such grid with zero padding the loss, the maps and the exports never
+        see.  Supported range on that network grid X x H x W: W <= 130 and H*W <= 7,667 (the LDS tile of bnt5's fused backward), so
+        91x109x91 -> 94x110x94 is refused here with a ValueError naming the layer -- schema.net_geometry), `xu_ranges` (inducing-point
         ranges given directly instead of read from `csv_files`), `tensorboard` (off by default),
         `data_parallel` (a dp.DataParallelContext), `gp_jitter` (0 = the reference's plain inverse of the
         inducing-point kernel matrix Ku, gp.py:104-107; > 0: Ku + gp_jitter*I on the unit-variance scale, i.e. the
@@ -135,6 +138,11 @@ class VAE(nn.Module):
         self.img_shape = tuple(int(v) for v in img_shape)
         self.img_dim = int(np.prod(self.img_shape))
         self.geom = net_geometry(self.img_shape, nf)
+        # the grid the layers run on and the zero voxels between it and the data's grid (schema.net_geometry); img_shape / img_dim,
+        # epsilon, glm_maps, the maps and the checkpoints are native
+        self.grid_shape, self.img_pad = tuple(self.geom.img), tuple(self.geom.pad)
+        self.grid_dim = int(np.prod(self.grid_shape))
+        self._embedded = any(self.img_pad)
         self.schema = covariate_schema(num_covariates, neural_covariates)
         self.dp = data_parallel
         assert dp_gain in ('local', 'global')
@@ -203,6 +211,11 @@ class VAE(nn.Module):
         sizes = {sp.name: (esz[i], esz[i + 1]) for i, sp in enumerate(self.geom.enc)}
         sizes.update({sp.name: (dsz[i], dsz[i + 1]) for i, sp in enumerate(self.geom.dec)})
         self._packed = ops.PackedWeights(convs, g32['p'], {n: off32[n + '.weight'] for n, _, _ in convs}, sizes)
+        # a derived grid is asked of the library's planners: here for its shape, and again per batch size before a step's first launch
+        self._plan_sizes = sizes if self.grid_shape not in ((41, 49, 35), (82, 98, 70), (21, 21, 21)) else None
+        self._plans_checked = set()
+        if self._plan_sizes is not None:
+            self._check_layer_plans(2)
         self.epoch = 0
         self.loss = {'train': {}, 'test': {}}
         ts = datetime.datetime.now().date()
@@ -254,6 +267,42 @@ class VAE(nn.Module):
         p = torch.nn.Parameter(value.to(self.device))
         setattr(self, attr_prefix + cov, p)
         self.gp_params[cov][key] = p
+
+    def _check_layer_plans(self, B):
+        """A derived grid (schema.net_geometry's family rule) is asked of every planner the library has, layer by layer, before
+        anything is launched: a grid a kernel has no launch plan for is refused here with the layer named (ValueError).  (The
+        matrix-core plans were built by PackedWeights; a layer without one runs on the register-tiled kernels.)
+        The constructor asks with a batch of 2, which settles what depends on the shape alone (LDS tiles, row widths); the
+        weight-gradient planner also weighs the batch when it picks a tile, so forward_core asks again with the batch of the step,
+        once per batch size, before that step's first launch.  With VG_FUSE_LAST_BN_BWD=0 the last stage takes the unfused batch-norm
+        backward, which has no planner of its own and has been run on the explicit shapes only."""
+        import ctypes
+        from . import _lib
+        lib = _lib.get_lib()                          # a missing library says so itself
+        sizes, B = self._plan_sizes, int(B)
+        G = self.num_covariates + 1
+        with_bn = ('conv1', 'conv3', 'conv5', 'convt1', 'convt3', 'convt5')
+        for sp in self.geom.enc + self.geom.dec:
+            isz, osz = sizes[sp.name]
+            n = B * (G if sp.kind == 'convt' else 1)
+            x_shape, dy_shape, relu_in = (n, sp.ci) + tuple(isz), (n, sp.co) + tuple(osz), sp.name != 'conv1'
+            try:
+                ops.wgrad_plan(sp, x_shape, dy_shape, relu_in, B)
+                lib.size('vg_wgrad3d_ws_bytes', ctypes.byref(ops.wgrad_desc(sp, x_shape, dy_shape, relu_in, B)[0]))
+                if sp.name in with_bn:
+                    ops.bn_plan(n, sp.ci, int(np.prod(isz)), B)
+                    lib.size('vg_bn_ws_bytes', n, sp.ci, int(np.prod(isz)), B)
+                if sp.name == 'convt5' and ops.FUSE_LAST_BN_BWD:      # bnt5's backward fused with convt5's data gradient stages planes of dy
+                    lib.size('vg_bn_tconv1_lds_bytes', sp.ci, *isz)
+                    lib.size('vg_bn_tconv1_ws_bytes', n, sp.ci, isz[0], B)
+            except _lib.VgError as e:
+                raise ValueError('image shape %r (network grid %r): layer %s has no launch plan: %s'
+                                 % (self.img_shape, self.grid_shape, sp.name, e))
+        try:
+            lib.size('vg_gam_ws_bytes', self.num_covariates, B, self.grid_dim)
+        except _lib.VgError as e:
+            raise ValueError('image shape %r (network grid %r): the GAM/ELBO kernels refuse it: %s' % (self.img_shape, self.grid_shape, e))
+        self._plans_checked.add(B)
 
     def _build_network(self):
         """Same layers, same registration (= RNG and named_parameters) order as vae_reg_GP.py:187-218.
@@ -313,7 +362,11 @@ class VAE(nn.Module):
         self._require_gpu(x)
         e = self.geom.enc
         B = x.shape[0]
-        h = x.reshape(B, 1, *self.img_shape).contiguous()
+        if self._embedded:
+            # one launch: the volumes zero-padded to the grid the layers run on (encode, project_latent and the train step share it)
+            h = ops.embed_volumes(x.float(), self.img_shape, self.grid_shape).view(B, 1, *self.grid_shape)
+        else:
+            h = x.reshape(B, 1, *self.img_shape).contiguous()
         s = self._sync()
         bca = ops.bn_conv_act
         # bias gradients of conv2 / conv4 come out of the batch-norm backward of the layers that consume them (bn3 / bn5)
@@ -351,7 +404,8 @@ class VAE(nn.Module):
         return mu, w.unsqueeze(-1), torch.exp(a)
 
     def _decode_logits(self, z, per_group, last_bias_by_consumer=False):
-        """z (N, z_dim), N = groups*per_group -> pre-sigmoid maps (N, V).  Batch-norm statistics are
+        """z (N, z_dim), N = groups*per_group -> pre-sigmoid maps (N, V_grid) on the grid the layers run on (= V but for an embedded
+        shape).  Batch-norm statistics are
         kept per group of `per_group` consecutive samples (one group per one-hot variant).
         last_bias_by_consumer: convt5's bias gradient is formed by the consumer of the logits (ops.GamElbo(..., logits_bias=))."""
         self._require_gpu(z)
@@ -374,13 +428,17 @@ class VAE(nn.Module):
                      next_bn=per_group, bias_grad_by_consumer=True, relu_out=r, rectified_in=r)
         p = bca(p, self.convt5.weight, self.convt5.bias, self.bnt5.weight, self.bnt5.bias, dsp[4], True, per_group, False, s, self._packed,
                 pre_stats=st5, producer_bias=self.convt4.bias, bias_grad_by_consumer=last_bias_by_consumer, rectified_in=r)
-        return p.reshape(p.shape[0], self.img_dim)
+        return p.reshape(p.shape[0], self.grid_dim)
 
     def decode(self, z):
-        """z (B, z_dim) -> sigmoid maps (B, V)   (vae_reg_GP.py:254-264)."""
+        """z (B, z_dim) -> sigmoid maps (B, V) on the native grid   (vae_reg_GP.py:254-264)."""
         self._require_gpu(z)
         self._packed.refresh()
-        return torch.sigmoid(self._decode_logits(z, z.shape[0]))
+        maps = torch.sigmoid(self._decode_logits(z, z.shape[0]))
+        if self._embedded:
+            n = self.img_shape
+            maps = maps.view(-1, *self.grid_shape)[:, :n[0], :n[1], :n[2]].reshape(-1, self.img_dim)
+        return maps
 
     # ------------------------------------------------------------------ probabilistic pieces
     def calc_linW_KL(self, sa, std):
@@ -492,13 +550,16 @@ class VAE(nn.Module):
     def forward_core(self, covariates, x, noise=None, want_maps=False):
         """The arithmetic of VAE.forward (vae_reg_GP.py:307-410), on device, no host syncs.
         Returns a dict of device tensors: loss (1,), z, mu, u, d, kl_z, task_var (C,B), gp_kl_loss,
-        dist (C,B; glm_reg = global batch * dist.sum()), sum_log_prob, logits (C+1,B,V) and, if asked, maps (C+2,B,V)."""
+        dist (C,B; glm_reg = global batch * dist.sum()), sum_log_prob, logits (C+1,B,V_grid: on the grid the layers run on) and, if
+        asked, maps (C+2,B,V) on the native grid."""
         B, C, L = x.shape[0], self.num_covariates, self.num_latents
         dev = x.device
         x = x.float()
         covariates = covariates[:, :C].float()           # the loaders always carry the reference's 8 columns; covariate i reads column i-1 (:345)
         self._require_gpu(x)                         # before ANY launch: host pointers must never reach a kernel
         self.check_gain_batch(B)                     # before ANY launch, too: the gain block's limit on the jointly drawn batch
+        if self._plan_sizes is not None and B not in self._plans_checked:
+            self._check_layer_plans(B)               # a derived grid: the planners' word on this batch size, layer by layer
         self._packed.refresh()                       # one launch: every conv weight -> the images the kernels read
         # data parallel (SURVEY 8e): this rank holds rows [lo, lo+B) of a global batch of Bg = world*B volumes
         W, lo, Bg = 1, 0, B
@@ -545,7 +606,7 @@ class VAE(nn.Module):
             mu, w, a = heads
             zcat, kl_z, d = ops.LatentSample.apply(mu, w, a, eps_w, eps_d, G)
         z, u = zcat[:B, :L], w.unsqueeze(-1)
-        logits = self._decode_logits(zcat, B, last_bias_by_consumer=True).view(G, B, self.img_dim)
+        logits = self._decode_logits(zcat, B, last_bias_by_consumer=True).view(G, B, self.grid_dim)
         task_var, gp_kl_loss, beta_mean, beta_cov, post = gains
         if gains_stream is not None:
             torch.cuda.current_stream(dev).wait_stream(gains_stream)
@@ -557,7 +618,11 @@ class VAE(nn.Module):
             conv = ops.HrfAcrossRanks.apply(task_var[hrf_rows], self._hrf_matrix(Bg, dev), self.dp, lo)
             task_var = torch.cat([conv[hrf_rows.index(i)].unsqueeze(0) if i in hrf_rows else task_var[i:i + 1] for i in range(C)], 0)
         xf = x.reshape(B, self.img_dim)
-        slp, dist = ops.GamElbo.apply(logits, task_var, xf, self.epsilon.view(-1), self._glm(), self.convt5.bias)
+        if self._embedded:       # logits on the grid, data / epsilon / GLM maps native; the padding gets a gradient of exactly zero
+            slp, dist = ops.GamElboEmbed.apply(logits, task_var, xf, self.epsilon.view(-1), self._glm(), self.img_shape, self.grid_shape,
+                                               self.convt5.bias)
+        else:
+            slp, dist = ops.GamElbo.apply(logits, task_var, xf, self.epsilon.view(-1), self._glm(), self.convt5.bias)
         # glm_reg = Bg * sum(dist) (:388-389, cdist's factor = global batch); elbo = sum(-kl_z + slp) / Bg (:406-408);
         # loss = -elbo + gp_kl_scale * gp_kl + glm_reg_scale * glm_reg (:410) -- one launch.  Replicated terms are
         # divided by the world size: the gradient all-reduce SUMS the per-rank losses.
@@ -567,7 +632,8 @@ class VAE(nn.Module):
                    sum_log_prob=slp, dist=dist, logits=logits, beta_mean=beta_mean, beta_cov=beta_cov,
                    gp_post=post)
         if want_maps:
-            out['maps'] = ops.gam_maps(logits.detach(), task_var.detach(), xf, self.epsilon.detach().view(-1), self._glm())
+            emb = (self.img_shape, self.grid_shape) if self._embedded else (None, None)
+            out['maps'] = ops.gam_maps(logits.detach(), task_var.detach(), xf, self.epsilon.detach().view(-1), self._glm(), *emb)
         return out
 
     def forward(self, ids, covariates, x, log_type, return_latent_rec=False, train_mode=True, noise=None):
