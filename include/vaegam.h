@@ -260,6 +260,18 @@ int vg_gam_elbo_bwd_embed(const float* logits, const float* gain, const float* x
                           const float* glm, const float* dist, const float* g_slp, const float* g_dist,
                           int32_t C, int32_t B, const int32_t* nat, const int32_t* grid, void* ws,
                           float* d_logits, float* d_gain, double* d_eps, float* d_total, int32_t total_accumulate, void* stream);
+/* The same pair restricted to a voxel mask: mask [V_N] bytes on the native grid, nonzero = the voxel counts.  A native voxel outside the
+ * mask takes no part, exactly like the padding: it adds nothing to sum_log_prob, dist, d_gain or d_total, d_logits is written as exact
+ * 0.f and d_eps as exact 0.0 there, and maps_out, when requested, as 0.f (every element of d_logits, d_eps and maps_out is written).
+ * nat == grid runs the kernels of the plain pair, any other nat those of the _embed pair, each instantiated with the mask test.
+ * ws: vg_gam_ws_bytes(C, B, V_G) bytes. */
+int vg_gam_elbo_fwd_masked(const float* logits, const float* gain, const float* x, const double* eps,
+                           const float* glm, const uint8_t* mask, int32_t C, int32_t B, const int32_t* nat, const int32_t* grid,
+                           void* ws, float* sum_log_prob, float* dist, float* maps_out, void* stream);
+int vg_gam_elbo_bwd_masked(const float* logits, const float* gain, const float* x, const double* eps,
+                           const float* glm, const uint8_t* mask, const float* dist, const float* g_slp, const float* g_dist,
+                           int32_t C, int32_t B, const int32_t* nat, const int32_t* grid, void* ws,
+                           float* d_logits, float* d_gain, double* d_eps, float* d_total, int32_t total_accumulate, void* stream);
 
 /* Batch-norm parameter gradients from vg_bn_bwd_reduce's per-(group, channel) sums:
  *   dgamma[c] (+)= sum_g sums[g][c][1],  dbeta[c] (+)= sum_g sums[g][c][0]   (accumulate != 0 adds into the .grad buffers;

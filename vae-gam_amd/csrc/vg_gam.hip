@@ -8,6 +8,9 @@
 // in ONE pass over the (C+1) x B x V logits instead of 3-4 elementwise passes per covariate plus
 // the (C+2) x B x V device-to-host copies, and the matching backward in one more pass.
 // HBM-streaming kernels: coalesced loads, per-wave shuffle reductions, fixed-order second stage.
+// Three entry-point pairs share the two kernels through compile-time flags: the plain pair (everything on one grid), the _embed pair
+// (logits on a larger grid than the data; the padding takes no part) and the _masked pair (a voxel mask on the data's grid, with or
+// without embedding; a voxel outside the mask takes no part, exactly like the padding).
 #include "vg_common.h"
 #include "../../include/vaegam.h"
 
@@ -62,27 +65,38 @@ embed_k(const float* __restrict__ x, float* __restrict__ out, long long V, GamGr
 // grid (vchunks, B).  part_slp[b][chunk], part_d2[i][b][chunk]
 // EMB: V counts the voxels of the grid the logits are on, x / eps / glm / maps_out are on the native grid e.Vn; a voxel of the padding
 // is skipped like one behind the end.  Without EMB e is not read and the native index is the voxel index.
-template <bool EMB>
+// MSK: mask[Vn] bytes on the native grid; a native voxel whose byte is 0 takes no part either -- it is skipped like one of the padding,
+// except that it has a place in maps_out, which is written as 0 there.  Without MSK mask is not read.
+template <bool EMB, bool MSK>
 __global__ void __launch_bounds__(GT)
 gam_fwd_k(const float* __restrict__ logits, const float* __restrict__ gain, const float* __restrict__ x,
           const double* __restrict__ eps, const float* __restrict__ glm, int C, int B, long long V,
-          float* __restrict__ part_slp, float* __restrict__ part_d2, float* __restrict__ maps_out, GamGrid e) {
+          float* __restrict__ part_slp, float* __restrict__ part_d2, float* __restrict__ maps_out, GamGrid e,
+          const uint8_t* __restrict__ mask) {
     __shared__ float red[GT / VG_WAVE][GMAXC + 1];
     const int chunk = blockIdx.x, b = blockIdx.y, chunks = gridDim.x;
     const int lane = threadIdx.x % VG_WAVE, wave = threadIdx.x / VG_WAVE;
     const long long v0 = (long long)chunk * GT * GV + threadIdx.x;
     float xrec[GV];
-    bool ok[GV];
+    bool ok[GV], out[GV];                                              // out: a native voxel outside the mask
     long long vn[GV];
 #pragma unroll
     for (int k = 0; k < GV; ++k) {
         vn[k] = v0 + (long long)k * GT;
         ok[k] = vn[k] < V;
         if (EMB) { const bool nat = grid_to_native(e, v0 + (long long)k * GT, vn[k]); ok[k] = ok[k] && nat; }
+        out[k] = false;
+        if (MSK) { const bool in = ok[k] && mask[vn[k]] != 0; out[k] = ok[k] && !in; ok[k] = in; }
         xrec[k] = 0.f;
     }
     const long long Vn = EMB ? e.Vn : V;
     const size_t BV = (size_t)B * V, BVn = (size_t)B * Vn;
+    if (MSK && maps_out) {
+#pragma unroll
+        for (int k = 0; k < GV; ++k)
+            if (out[k])
+                for (int g = 0; g <= C + 1; ++g) maps_out[(size_t)g * BVn + (size_t)b * Vn + vn[k]] = 0.f;
+    }
     // base map
 #pragma unroll
     for (int k = 0; k < GV; ++k)
@@ -151,13 +165,15 @@ gam_fwd_fold_k(const float* __restrict__ part_slp, const float* __restrict__ par
 // sample: 228 us at batch 64 / 8 covariates against 60 us of HBM time).
 // EMB: as in gam_fwd_k; a thread on a voxel of the padding loads from clamped addresses like one behind the end, writes d_logits = 0
 // and adds nothing to any sum.  part_dsig is [bs][Vn].
-template <int CMAX, bool EMB>
+// MSK: as in gam_fwd_k; a thread on a native voxel outside the mask behaves like one of the padding and stores a 0 partial in part_dsig,
+// which gam_bwd_fold_eps_k reads for every native voxel (d_eps = 0 there, not what the workspace held).
+template <int CMAX, bool EMB, bool MSK>
 __global__ void __launch_bounds__(GT)
 gam_bwd_k(const float* __restrict__ logits, const float* __restrict__ gain, const float* __restrict__ x,
           const double* __restrict__ eps, const float* __restrict__ glm, const float* __restrict__ dist,
           const float* __restrict__ g_slp, const float* __restrict__ g_dist, int C, int B, long long V,
           float* __restrict__ d_logits, float* __restrict__ part_dsig, float* __restrict__ part_dgain, float* __restrict__ part_tot,
-          GamGrid e) {
+          GamGrid e, const uint8_t* __restrict__ mask) {
     const int vb = blockIdx.x, bs = blockIdx.y, BS = gridDim.y, nparts = gridDim.x * (GT / VG_WAVE);
     const int lane = threadIdx.x % VG_WAVE, wave = threadIdx.x / VG_WAVE;
     const long long v = (long long)vb * GT + threadIdx.x;
@@ -166,6 +182,8 @@ gam_bwd_k(const float* __restrict__ logits, const float* __restrict__ gain, cons
     long long nc = vc;                                                 // the voxel's index in the native tensors, clamped likewise
     bool nat = ok;                                                     // a voxel that counts
     if (EMB) { nat = grid_to_native(e, vc, nc) && ok; if (!nat) nc = 0; }
+    const bool native = nat;                                           // a voxel that has a place in the native tensors
+    if (MSK) nat = nat && mask[nc] != 0;
     const long long Vn = EMB ? e.Vn : V;
     const size_t BV = (size_t)B * V;
     const float sg = (float)exp(-eps[nc]), inv_var = 1.f / (sg * sg);
@@ -194,7 +212,7 @@ gam_bwd_k(const float* __restrict__ logits, const float* __restrict__ gain, cons
             dsig += gs * (r * r * inv_var / sg - 1.f / sg);            // d slp / d sigma
             const float dl = dxr * sgm[0] * (1.f - sgm[0]);
             d_logits[row] = dl; tot += dl;
-        } else if (EMB && ok) d_logits[row] = 0.f;
+        } else if ((EMB || MSK) && ok) d_logits[row] = 0.f;
 #pragma unroll
         for (int i = 0; i < CMAX; ++i) {
             if (i < C) {                                               // wave-uniform
@@ -204,13 +222,14 @@ gam_bwd_k(const float* __restrict__ logits, const float* __restrict__ gain, cons
                 if (dd > 0.f) dcons += g_dist[(size_t)i * B + b] * (gn[i] * s_ - glm_v[i]) / dd;
                 const float dl = dcons * gn[i] * s_ * (1.f - s_);
                 if (nat) { d_logits[(size_t)(i + 1) * BV + row] = dl; tot += dl; }
-                else if (EMB && ok) d_logits[(size_t)(i + 1) * BV + row] = 0.f;
+                else if ((EMB || MSK) && ok) d_logits[(size_t)(i + 1) * BV + row] = 0.f;
                 const float dg = wsum(nat ? dcons * s_ : 0.f);
                 if (lane == 0) part_dgain[((size_t)i * B + b) * nparts + vb * (GT / VG_WAVE) + wave] = dg;
             }
         }
     }
     if (nat) part_dsig[(size_t)bs * Vn + nc] = dsig;
+    else if (MSK && native) part_dsig[(size_t)bs * Vn + nc] = 0.f;
     if (part_tot) {
         tot = wsum(tot);
         if (lane == 0) part_tot[((size_t)bs * gridDim.x + vb) * (GT / VG_WAVE) + wave] = tot;
@@ -469,10 +488,10 @@ long long make_grid(const int32_t* nat, const int32_t* grid, GamGrid& e) {
 }
 
 int gam_fwd(const float* logits, const float* gain, const float* x, const double* eps, const float* glm, int32_t C, int32_t B, int64_t V,
-            const GamGrid* e, void* ws, float* sum_log_prob, float* dist, float* maps_out, void* stream);
+            const GamGrid* e, const uint8_t* mask, void* ws, float* sum_log_prob, float* dist, float* maps_out, void* stream);
 int gam_bwd(const float* logits, const float* gain, const float* x, const double* eps, const float* glm, const float* dist,
-            const float* g_slp, const float* g_dist, int32_t C, int32_t B, int64_t V, const GamGrid* e, void* ws,
-            float* d_logits, float* d_gain, double* d_eps, float* d_total, int32_t total_accumulate, void* stream);
+            const float* g_slp, const float* g_dist, int32_t C, int32_t B, int64_t V, const GamGrid* e, const uint8_t* mask,
+            void* ws, float* d_logits, float* d_gain, double* d_eps, float* d_total, int32_t total_accumulate, void* stream);
 
 }  // namespace
 
@@ -487,7 +506,7 @@ extern "C" int vg_embed_volumes(const float* x, const int32_t* nat, const int32_
 extern "C" int vg_gam_elbo_fwd(const float* logits, const float* gain, const float* x, const double* eps,
                                const float* glm, int32_t C, int32_t B, int64_t V, void* ws,
                                float* sum_log_prob, float* dist, float* maps_out, void* stream) {
-    return gam_fwd(logits, gain, x, eps, glm, C, B, V, nullptr, ws, sum_log_prob, dist, maps_out, stream);
+    return gam_fwd(logits, gain, x, eps, glm, C, B, V, nullptr, nullptr, ws, sum_log_prob, dist, maps_out, stream);
 }
 
 extern "C" int vg_gam_elbo_fwd_embed(const float* logits, const float* gain, const float* x, const double* eps,
@@ -496,14 +515,14 @@ extern "C" int vg_gam_elbo_fwd_embed(const float* logits, const float* gain, con
     GamGrid e;
     const long long V = make_grid(nat, grid, e);
     if (V < 0) { vg_set_error("vg_gam_elbo_fwd_embed: the native grid must fit into a grid of less than 2^31 voxels"); return VG_ERR_ARG; }
-    return gam_fwd(logits, gain, x, eps, glm, C, B, V, &e, ws, sum_log_prob, dist, maps_out, stream);
+    return gam_fwd(logits, gain, x, eps, glm, C, B, V, &e, nullptr, ws, sum_log_prob, dist, maps_out, stream);
 }
 
 extern "C" int vg_gam_elbo_bwd(const float* logits, const float* gain, const float* x, const double* eps,
                                const float* glm, const float* dist, const float* g_slp, const float* g_dist,
                                int32_t C, int32_t B, int64_t V, void* ws,
                                float* d_logits, float* d_gain, double* d_eps, float* d_total, int32_t total_accumulate, void* stream) {
-    return gam_bwd(logits, gain, x, eps, glm, dist, g_slp, g_dist, C, B, V, nullptr, ws, d_logits, d_gain, d_eps, d_total, total_accumulate, stream);
+    return gam_bwd(logits, gain, x, eps, glm, dist, g_slp, g_dist, C, B, V, nullptr, nullptr, ws, d_logits, d_gain, d_eps, d_total, total_accumulate, stream);
 }
 
 extern "C" int vg_gam_elbo_bwd_embed(const float* logits, const float* gain, const float* x, const double* eps,
@@ -513,14 +532,37 @@ extern "C" int vg_gam_elbo_bwd_embed(const float* logits, const float* gain, con
     GamGrid e;
     const long long V = make_grid(nat, grid, e);
     if (V < 0) { vg_set_error("vg_gam_elbo_bwd_embed: the native grid must fit into a grid of less than 2^31 voxels"); return VG_ERR_ARG; }
-    return gam_bwd(logits, gain, x, eps, glm, dist, g_slp, g_dist, C, B, V, &e, ws, d_logits, d_gain, d_eps, d_total, total_accumulate, stream);
+    return gam_bwd(logits, gain, x, eps, glm, dist, g_slp, g_dist, C, B, V, &e, nullptr, ws, d_logits, d_gain, d_eps, d_total, total_accumulate, stream);
+}
+
+// nat == grid: the kernels without the index decode, as the plain pair; any other nat: those of the _embed pair
+extern "C" int vg_gam_elbo_fwd_masked(const float* logits, const float* gain, const float* x, const double* eps,
+                                      const float* glm, const uint8_t* mask, int32_t C, int32_t B, const int32_t* nat, const int32_t* grid,
+                                      void* ws, float* sum_log_prob, float* dist, float* maps_out, void* stream) {
+    GamGrid e;
+    const long long V = make_grid(nat, grid, e);
+    if (V < 0) { vg_set_error("vg_gam_elbo_fwd_masked: the native grid must fit into a grid of less than 2^31 voxels"); return VG_ERR_ARG; }
+    if (!mask) { vg_set_error("vg_gam_elbo_fwd_masked: no mask"); return VG_ERR_ARG; }
+    return gam_fwd(logits, gain, x, eps, glm, C, B, V, e.Vn == V ? nullptr : &e, mask, ws, sum_log_prob, dist, maps_out, stream);
+}
+
+extern "C" int vg_gam_elbo_bwd_masked(const float* logits, const float* gain, const float* x, const double* eps,
+                                      const float* glm, const uint8_t* mask, const float* dist, const float* g_slp, const float* g_dist,
+                                      int32_t C, int32_t B, const int32_t* nat, const int32_t* grid, void* ws,
+                                      float* d_logits, float* d_gain, double* d_eps, float* d_total, int32_t total_accumulate, void* stream) {
+    GamGrid e;
+    const long long V = make_grid(nat, grid, e);
+    if (V < 0) { vg_set_error("vg_gam_elbo_bwd_masked: the native grid must fit into a grid of less than 2^31 voxels"); return VG_ERR_ARG; }
+    if (!mask) { vg_set_error("vg_gam_elbo_bwd_masked: no mask"); return VG_ERR_ARG; }
+    return gam_bwd(logits, gain, x, eps, glm, dist, g_slp, g_dist, C, B, V, e.Vn == V ? nullptr : &e, mask, ws, d_logits, d_gain, d_eps, d_total,
+                   total_accumulate, stream);
 }
 
 namespace {
 
-// V: voxels of the tensor the logits are on; emb: the embedded grid, or nullptr (everything on one grid)
+// V: voxels of the tensor the logits are on; emb: the embedded grid, or nullptr (everything on one grid); mask: [Vn] bytes, or nullptr
 int gam_fwd(const float* logits, const float* gain, const float* x, const double* eps, const float* glm, int32_t C, int32_t B, int64_t V,
-            const GamGrid* emb, void* ws, float* sum_log_prob, float* dist, float* maps_out, void* stream) {
+            const GamGrid* emb, const uint8_t* mask, void* ws, float* sum_log_prob, float* dist, float* maps_out, void* stream) {
     if (!logits || !x || !eps || !ws || !sum_log_prob || (C > 0 && (!gain || !glm || !dist)) || C < 0 || C > GMAXC || B <= 0 ||
         B > 65535 || V <= 0) {
         vg_set_error("vg_gam_elbo_fwd: bad arguments C=%d B=%d V=%lld", C, B, (long long)V); return VG_ERR_ARG;
@@ -529,12 +571,13 @@ int gam_fwd(const float* logits, const float* gain, const float* x, const double
     const int chunks = fwd_chunks(V);
     float* part_slp = (float*)ws;
     float* part_d2 = part_slp + (size_t)B * chunks;
-    if (emb)
-        vg_launch(gam_fwd_k<true>, dim3(chunks, B), dim3(GT), 0, s, logits, gain, x, eps, glm, (int)C, (int)B, (long long)V, part_slp, part_d2,
-                  maps_out, *emb);
-    else
-        vg_launch(gam_fwd_k<false>, dim3(chunks, B), dim3(GT), 0, s, logits, gain, x, eps, glm, (int)C, (int)B, (long long)V, part_slp, part_d2,
-                  maps_out, GamGrid{});
+    const GamGrid e = emb ? *emb : GamGrid{};
+#define VG_GAM_FWD(EMB, MSK)                                                                                                               \
+    vg_launch(gam_fwd_k<EMB, MSK>, dim3(chunks, B), dim3(GT), 0, s, logits, gain, x, eps, glm, (int)C, (int)B, (long long)V, part_slp, part_d2, \
+              maps_out, e, mask)
+    if (mask) { if (emb) VG_GAM_FWD(true, true); else VG_GAM_FWD(false, true); }
+    else { if (emb) VG_GAM_FWD(true, false); else VG_GAM_FWD(false, false); }
+#undef VG_GAM_FWD
     int rc = vg_check_launch("gam_fwd");
     if (rc) return rc;
     vg_launch(gam_fwd_fold_k, dim3((C + 1) * B), dim3(64), 0, s, (const float*)part_slp, (const float*)part_d2,
@@ -543,8 +586,8 @@ int gam_fwd(const float* logits, const float* gain, const float* x, const double
 }
 
 int gam_bwd(const float* logits, const float* gain, const float* x, const double* eps, const float* glm, const float* dist,
-            const float* g_slp, const float* g_dist, int32_t C, int32_t B, int64_t V, const GamGrid* emb, void* ws,
-            float* d_logits, float* d_gain, double* d_eps, float* d_total, int32_t total_accumulate, void* stream) {
+            const float* g_slp, const float* g_dist, int32_t C, int32_t B, int64_t V, const GamGrid* emb, const uint8_t* mask,
+            void* ws, float* d_logits, float* d_gain, double* d_eps, float* d_total, int32_t total_accumulate, void* stream) {
     if (!logits || !x || !eps || !ws || !g_slp || !d_logits || !d_eps || (C > 0 && (!gain || !glm || !dist || !g_dist || !d_gain)) ||
         C < 0 || C > GMAXC || B <= 0 || V <= 0) {
         vg_set_error("vg_gam_elbo_bwd: bad arguments C=%d B=%d V=%lld", C, B, (long long)V); return VG_ERR_ARG;
@@ -556,12 +599,16 @@ int gam_bwd(const float* logits, const float* gain, const float* x, const double
     float* part_tot = d_total ? part_dgain + (size_t)C * B * bwd_gain_parts(V) : nullptr;
     const GamGrid e = emb ? *emb : GamGrid{};
     const long long Vn = emb ? emb->Vn : (long long)V;                   // voxels of x / eps / d_eps
-#define VG_GAM_BWD(CMAX, EMB)                                                                                                     \
-    vg_launch(gam_bwd_k<CMAX, EMB>, dim3(vblocks, BS), dim3(GT), 0, s, logits, gain, x, eps, glm, dist, g_slp, g_dist, (int)C, (int)B, \
-              (long long)V, d_logits, part_dsig, part_dgain, part_tot, e)
-    if (C <= 8) { if (emb) VG_GAM_BWD(8, true); else VG_GAM_BWD(8, false); }
-    else if (C <= 16) { if (emb) VG_GAM_BWD(16, true); else VG_GAM_BWD(16, false); }
+#define VG_GAM_BWD(CMAX, EMB, MSK)                                                                                                     \
+    vg_launch(gam_bwd_k<CMAX, EMB, MSK>, dim3(vblocks, BS), dim3(GT), 0, s, logits, gain, x, eps, glm, dist, g_slp, g_dist, (int)C, (int)B, \
+              (long long)V, d_logits, part_dsig, part_dgain, part_tot, e, mask)
+#define VG_GAM_BWD_C(CMAX)                                                                  \
+    if (mask) { if (emb) VG_GAM_BWD(CMAX, true, true); else VG_GAM_BWD(CMAX, false, true); } \
+    else { if (emb) VG_GAM_BWD(CMAX, true, false); else VG_GAM_BWD(CMAX, false, false); }
+    if (C <= 8) { VG_GAM_BWD_C(8) }
+    else if (C <= 16) { VG_GAM_BWD_C(16) }
     else { vg_set_error("vg_gam_elbo_bwd: more than 16 covariates"); return VG_ERR_UNSUPPORTED; }
+#undef VG_GAM_BWD_C
 #undef VG_GAM_BWD
     int rc = vg_check_launch("gam_bwd");
     if (rc) return rc;

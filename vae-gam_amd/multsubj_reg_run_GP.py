@@ -62,6 +62,10 @@ def build_parser():
                              'whose axes are not all = 2 (mod 4) is zero-padded by up to 3 voxels per axis inside the network, while the '
                              'loss and every exported map stay on the grid given here.  The padded grid X x H x W must have W <= 130 and '
                              'H*W <= 7667 (91 109 91 -> 94x110x94 is refused).')
+    parser.add_argument('--mask', type=str, metavar='PATH', default='',
+                        help='(extension) Brain mask of --img_shape (.nii, .nii.gz or .npy; nonzero = in-brain; the first volume of a 4-D '
+                             'file).  The log-likelihood and the GLM distance sum over the voxels of the mask only, and every exported map '
+                             'is 0 outside it.  Default: every voxel counts, as the reference.')
     return parser
 
 
@@ -76,6 +80,24 @@ def check_img_shape(img_shape, loaders):
     if found != tuple(img_shape):
         raise ValueError('--img_shape is %s but the volumes of %s have the spatial shape %s'
                          % ('x'.join(map(str, img_shape)), path, 'x'.join(map(str, found))))
+
+
+def check_mask(mask_path, img_shape):
+    """--mask read and checked against --img_shape before the model is built: SystemExit for a file that is missing or of an unknown
+    kind, ValueError for a mask of another shape or with no voxel set.  Returns the mask array, or None without --mask."""
+    if not mask_path:
+        return None
+    if not os.path.exists(mask_path):
+        raise SystemExit('--mask %s does not exist' % mask_path)
+    if not mask_path.endswith(('.nii', '.nii.gz', '.npy')):
+        raise SystemExit('--mask %s: expected a .nii, .nii.gz or .npy file' % mask_path)
+    mask = vae_reg.VAE.read_mask(mask_path)
+    if tuple(mask.shape) != tuple(img_shape):
+        raise ValueError('--img_shape is %s but the mask %s has the spatial shape %s'
+                         % ('x'.join(map(str, img_shape)), mask_path, 'x'.join(map(str, mask.shape))))
+    if not (mask != 0).any():
+        raise ValueError('--mask %s has no voxel set' % mask_path)
+    return mask
 
 
 def main(argv=None):
@@ -94,6 +116,7 @@ def main(argv=None):
     if dp is not None and args.batch_size % dp.world_size:
         raise SystemExit('--batch-size %d (the GLOBAL minibatch) must be a multiple of the %d ranks' % (args.batch_size, dp.world_size))
     check_batch_size(args.batch_size, 1 if dp is None else dp.world_size, os.environ.get('VG_DP_GAIN', 'global'))
+    mask = check_mask(args.mask, args.img_shape)
     # the reference's loaders (whole data set, GLOBAL minibatch, multsubj_reg_run_GP.py:69): what the export pipeline iterates -- gains
     # (joint draw, HRF along the batch) and the decoder's batch statistics depend on the batch composition, so the exported maps must
     # see the batches a single process would; under data parallelism the train / test loops get re-built loaders that hand each rank
@@ -114,7 +137,7 @@ def main(argv=None):
                         glm_reg_scale=args.glm_reg_scale, glm_maps=args.glm_maps, save_dir=args.save_dir,
                         csv_files=[args.train_csv, args.test_csv], neural_covariates=args.neural_covariates,
                         data_parallel=dp, dp_gain=os.environ.get('VG_DP_GAIN', 'global'), gp_jitter=args.gp_jitter,
-                        max_grad_norm=args.max_grad_norm, skip_nonfinite=args.skip_nonfinite, img_shape=tuple(args.img_shape))
+                        max_grad_norm=args.max_grad_norm, skip_nonfinite=args.skip_nonfinite, img_shape=tuple(args.img_shape), mask=mask)
     model.use_hip_graph = bool(args.hip_graph)
     if args.from_ckpt:
         assert os.path.exists(args.ckpt_path), 'Oops, looks like ckpt file given does NOT exist!'

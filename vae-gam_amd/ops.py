@@ -752,8 +752,18 @@ def _i3(v):
     return (ctypes.c_int32 * 3)(*v)
 
 
-def _gam_forward(ctx, logits, gain, x, eps, glm, logits_bias, nat=None, grid=None):
-    """forward of GamElbo (nat is None: everything on one grid) and GamElboEmbed"""
+def _chk_mask(mask, Vn, like):
+    """the voxel mask of the _masked entry points: [V_nat] uint8 on the data's device"""
+    if mask.dtype != torch.uint8 or mask.device != like.device:
+        raise ValueError(f'mask must be a uint8 tensor on {like.device}, got {mask.dtype} on {mask.device}')
+    mask = mask.reshape(-1).contiguous()
+    if mask.numel() != Vn:
+        raise ValueError(f'mask has {mask.numel()} voxels, the native grid {Vn}')
+    return mask
+
+
+def _gam_forward(ctx, logits, gain, x, eps, glm, logits_bias, nat=None, grid=None, mask=None):
+    """forward of GamElbo (nat is None: everything on one grid), GamElboEmbed and GamElboMasked (mask given; nat may equal grid)"""
     lib = _lib.get_lib()
     G, B, V = logits.shape
     C = G - 1
@@ -762,7 +772,13 @@ def _gam_forward(ctx, logits, gain, x, eps, glm, logits_bias, nat=None, grid=Non
     ws = torch.empty(lib.size('vg_gam_ws_bytes', C, B, V) // 4 + 1, dtype=torch.float32, device=x.device)
     slp = torch.empty(B, dtype=torch.float32, device=x.device)
     dist = torch.empty((C, B), dtype=torch.float32, device=x.device)
-    if nat is None:
+    if mask is not None:
+        Vn = nat[0] * nat[1] * nat[2]
+        assert V == grid[0] * grid[1] * grid[2] and x.shape == (B, Vn) and eps.shape == (Vn,) and (C == 0 or glm.shape == (C, Vn))
+        mask = _chk_mask(mask, Vn, x)
+        _call(x, 'vg_gam_elbo_fwd_masked', _p(logits), _p(gain), _p(x), _p(eps), _p(glm), _p(mask), C, B, _i3(nat), _i3(grid), _p(ws),
+                 _p(slp), _p(dist), None)
+    elif nat is None:
         _call(x, 'vg_gam_elbo_fwd', _p(logits), _p(gain), _p(x), _p(eps), _p(glm), C, B, V, _p(ws), _p(slp), _p(dist),
                  None)
     else:
@@ -771,7 +787,7 @@ def _gam_forward(ctx, logits, gain, x, eps, glm, logits_bias, nat=None, grid=Non
         _call(x, 'vg_gam_elbo_fwd_embed', _p(logits), _p(gain), _p(x), _p(eps), _p(glm), C, B, _i3(nat), _i3(grid), _p(ws), _p(slp),
                  _p(dist), None)
     ctx.save_for_backward(logits, gain, x, eps, glm, dist)
-    ctx.logits_bias, ctx.nat, ctx.grid = logits_bias, nat, grid
+    ctx.logits_bias, ctx.nat, ctx.grid, ctx.mask = logits_bias, nat, grid, mask
     return slp, dist
 
 
@@ -793,7 +809,10 @@ def _gam_backward(ctx, g_slp, g_dist):
     d_logits = torch.empty_like(logits)
     d_gain = torch.empty_like(gain)
     d_eps = torch.empty_like(eps)
-    if ctx.nat is None:
+    if ctx.mask is not None:
+        _call(x, 'vg_gam_elbo_bwd_masked', _p(logits), _p(gain), _p(x), _p(eps), _p(glm), _p(ctx.mask), _p(dist), _p(g_slp), _p(g_dist),
+                 C, B, _i3(ctx.nat), _i3(ctx.grid), _p(ws), _p(d_logits), _p(d_gain), _p(d_eps), _p(tot), 1)
+    elif ctx.nat is None:
         _call(x, 'vg_gam_elbo_bwd', _p(logits), _p(gain), _p(x), _p(eps), _p(glm), _p(dist), _p(g_slp), _p(g_dist),
                  C, B, V, _p(ws), _p(d_logits), _p(d_gain), _p(d_eps), _p(tot), 1)
     else:
@@ -831,6 +850,21 @@ class GamElboEmbed(torch.autograd.Function):
     def backward(ctx, g_slp, g_dist):
         d_logits, d_gain, d_eps = _gam_backward(ctx, g_slp, g_dist)
         return d_logits, d_gain, None, d_eps, None, None, None, None
+
+
+class GamElboMasked(torch.autograd.Function):
+    """GamElbo / GamElboEmbed restricted to a voxel mask: `mask` is a uint8 tensor of V_nat voxels on the native grid `nat` (which may
+    equal `grid`), nonzero = the voxel counts.  (sum_log_prob[B], dist[C,B]) run over the voxels of the mask only; the gradients of the
+    logits and of eps are exactly zero at every other voxel, padding included.  The mask has no gradient.  `logits_bias`: as in GamElbo."""
+
+    @staticmethod
+    def forward(ctx, logits, gain, x, eps, glm, mask, nat, grid, logits_bias=None):
+        return _gam_forward(ctx, logits, gain, x, eps, glm, logits_bias, tuple(int(a) for a in nat), tuple(int(a) for a in grid), mask)
+
+    @staticmethod
+    def backward(ctx, g_slp, g_dist):
+        d_logits, d_gain, d_eps = _gam_backward(ctx, g_slp, g_dist)
+        return d_logits, d_gain, None, d_eps, None, None, None, None, None
 
 
 def embed_volumes(x, nat, grid):
@@ -1073,9 +1107,10 @@ def linear_act(layer, x, relu, relu_in=False):
     return LinearAct.apply(x, layer.weight, layer.bias, relu, relu_in)
 
 
-def gam_maps(logits, gain, x, eps, glm, nat=None, grid=None):
+def gam_maps(logits, gain, x, eps, glm, nat=None, grid=None, mask=None):
     """Reconstruction path (vae_reg_GP.py:331,391-392): the C+2 maps [base, cons_1..C, full_rec] as [C+2,B,V].
-    With nat / grid (see GamElboEmbed) the logits are on the grid and the maps come out on the native grid: V = V_nat."""
+    With nat / grid (see GamElboEmbed) the logits are on the grid and the maps come out on the native grid: V = V_nat.
+    With mask (see GamElboMasked; needs nat and grid, which may be equal) every map is exactly 0 outside the mask."""
     lib = _lib.get_lib()
     G, B, V = logits.shape
     C = G - 1
@@ -1086,7 +1121,10 @@ def gam_maps(logits, gain, x, eps, glm, nat=None, grid=None):
     maps = torch.empty((G + 1, B, Vn), dtype=torch.float32, device=x.device)
     ptrs = (_p(_chk(logits.contiguous())), _p(_chk(gain.contiguous())), _p(_chk(x.contiguous())),
             _p(_chk(eps.contiguous(), torch.float64)), _p(_chk(glm.contiguous())))
-    if nat is None:
+    if mask is not None:
+        assert V == int(grid[0]) * int(grid[1]) * int(grid[2]) and x.shape == (B, Vn)
+        _call(x, 'vg_gam_elbo_fwd_masked', *ptrs, _p(_chk_mask(mask, Vn, x)), C, B, _i3(nat), _i3(grid), _p(ws), _p(slp), _p(dist), _p(maps))
+    elif nat is None:
         _call(x, 'vg_gam_elbo_fwd', *ptrs, C, B, V, _p(ws), _p(slp), _p(dist), _p(maps))
     else:
         assert V == int(grid[0]) * int(grid[1]) * int(grid[2]) and x.shape == (B, Vn)

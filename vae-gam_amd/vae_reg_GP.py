@@ -10,6 +10,8 @@ train step runs on hand-written HIP kernels through the C ABI of include/vaegam.
     conv kernel while it stages its LDS tile, ReLU backward is fused into the data-gradient epilogue;
   * effect-map scaling, accumulation, Gaussian log-likelihood and the GLM distance are one fused
     kernel (`GamElbo`), with no (C+2)*B*V device-to-host copies unless maps are asked for;
+  * with a brain mask (`VAE(mask=...)`) the same kernel runs over the voxels of the mask only (`GamElboMasked`): the other voxels
+    add nothing to the loss, get gradients of exactly zero and come out of the exports as zeros;
   * the sparse-GP gains of all continuous covariates are evaluated batched, without host syncs;
   * parameters live in one flat HBM buffer updated by a fused Adam (optim.FusedAdam).
 
@@ -97,7 +99,7 @@ class VAE(nn.Module):
     def __init__(self, nf=8, save_dir='', lr=1e-3, num_covariates=8, num_latents=32, device_name="auto",
                  num_inducing_pts=6, gp_kl_scale=10.0, glm_maps='', glm_reg_scale=1.0, csv_files='',
                  neural_covariates=True, *, img_shape=IMG_SHAPE, xu_ranges=None, tensorboard=False,
-                 data_parallel=None, gp_jitter=0.0, dp_gain='global', max_grad_norm=None, skip_nonfinite=False):
+                 data_parallel=None, gp_jitter=0.0, dp_gain='global', max_grad_norm=None, skip_nonfinite=False, mask=None):
         """Arguments up to `neural_covariates` are the reference's (vae_reg_GP.py:36-37).
         Keyword-only extensions: `img_shape` (the data's grid: 41x49x35, 82x98x70 and grids with every axis = 2 (mod 4) run as they
         are, any other with axes >= 19 is embedded into the next such grid with zero padding the loss, the maps and the exports never
@@ -127,6 +129,13 @@ class VAE(nn.Module):
         holds an inf / nan into a no-op (parameters, Adam moments and Adam's step count untouched) instead of writing it into every
         parameter.  No host read-back, so it is captured into the hipGraph with the rest of the step.  The clip factor is applied as
         the update reads the gradient: `p.grad` stays the raw gradient.  Counters: optimizer.guard_stats().
+        `mask` (default None: every voxel counts, as the reference): a brain mask of `img_shape` -- an array or tensor of any dtype,
+        nonzero = in-brain, or a path to a .nii / .nii.gz / .npy file (the first volume of a 4-D one).  The log-likelihood and the GLM
+        distance then sum over the voxels of the mask only (same formula and constants, no renormalisation), every exported map is
+        exactly 0 outside it, and the log-precision map gets a gradient of exactly 0 there, so Adam leaves it at its value.  The data
+        batch-norm (bn1) and the encoder still see the whole volume.  A mask of another shape or with no voxel set raises ValueError.
+        Kept as `self.mask` (uint8, native shape, on the device) and `self.mask_voxels`; written into checkpoints, and load_state adopts
+        a checkpoint's mask.
         `glm_maps` may be a CSV path
         (reference) or an array of shape (V, C+1) whose column 0 is the CSV index column."""
         super(VAE, self).__init__()
@@ -216,6 +225,9 @@ class VAE(nn.Module):
         self._plans_checked = set()
         if self._plan_sizes is not None:
             self._check_layer_plans(2)
+        self.mask, self.mask_voxels = None, None
+        self._graphs = {}
+        self.set_mask(mask)
         self.epoch = 0
         self.loss = {'train': {}, 'test': {}}
         ts = datetime.datetime.now().date()
@@ -229,12 +241,50 @@ class VAE(nn.Module):
         self._glm_f32 = None
         self.use_hip_graph = False     # capture the train step into a hipGraph (bench / long runs)
         self.recon_sums = None         # per-subject map sums left by reconstruct() for build_model_recons.mk_avg_maps
-        self._graphs = {}
         self.last_gp_kl = None
         # decoder hand-off: convt1..convt4 store their outputs rectified and convt2..convt5 are told so (ops.BnConvAct: relu_out /
         # rectified_in) -- bit-identical results, prologue-free forwards of convt2 and convt4.  Off: everything stored pre-activation.
         # (a captured step holds the launches of the setting it was captured with)
         self.rectified_handoff = True
+
+    # ------------------------------------------------------------------ brain mask
+    @staticmethod
+    def read_mask(mask):
+        """A mask given as a path (.nii / .nii.gz / .npy; the first volume of a 4-D file), an array or a tensor -> numpy array"""
+        if isinstance(mask, (str, os.PathLike)):
+            from . import DataClass_GP as data
+            path = os.fspath(mask)
+            if path.endswith('.npy'):
+                mask = np.load(path)
+            elif path.endswith(('.nii', '.nii.gz')):
+                mask = data.read_nifti1(path)
+            else:
+                raise ValueError('mask file %s: expected .nii, .nii.gz or .npy' % path)
+            if mask.ndim == 4:
+                mask = mask[..., 0]
+        if torch.is_tensor(mask):
+            mask = mask.detach().cpu().numpy()
+        return np.asarray(mask)
+
+    def set_mask(self, mask):
+        """Set (or, with None, drop) the brain mask of a built model (see __init__).  Captured steps hold the launches and the mask
+        pointer of the previous setting, so the graphs are dropped and re-captured on the next train_step."""
+        if mask is None:
+            new, count = None, None
+        else:
+            m = self.read_mask(mask)
+            if tuple(m.shape) != self.img_shape:
+                raise ValueError('mask has the shape %s, the model\'s img_shape is %s'
+                                 % ('x'.join(map(str, m.shape)), 'x'.join(map(str, self.img_shape))))
+            m = np.ascontiguousarray(m != 0).astype(np.uint8)
+            count = int(m.sum())
+            if count == 0:
+                raise ValueError('mask has no voxel set: nothing would be left of the loss')
+            new = torch.from_numpy(m).to(self.device)
+        if self._graphs and self.device.type == 'cuda':
+            torch.cuda.current_stream(self.device).synchronize()     # queued replays still read the mask about to be released
+        self.mask, self.mask_voxels = new, count
+        self._graphs.clear()
 
     # ------------------------------------------------------------------ gradient guard
     @property
@@ -618,7 +668,10 @@ class VAE(nn.Module):
             conv = ops.HrfAcrossRanks.apply(task_var[hrf_rows], self._hrf_matrix(Bg, dev), self.dp, lo)
             task_var = torch.cat([conv[hrf_rows.index(i)].unsqueeze(0) if i in hrf_rows else task_var[i:i + 1] for i in range(C)], 0)
         xf = x.reshape(B, self.img_dim)
-        if self._embedded:       # logits on the grid, data / epsilon / GLM maps native; the padding gets a gradient of exactly zero
+        if self.mask is not None:   # the ELBO and the GLM distance over the voxels of the mask; every other voxel, padding included,
+            slp, dist = ops.GamElboMasked.apply(logits, task_var, xf, self.epsilon.view(-1), self._glm(), self.mask, self.img_shape,
+                                                self.grid_shape, self.convt5.bias)          # gets a gradient of exactly zero
+        elif self._embedded:     # logits on the grid, data / epsilon / GLM maps native; the padding gets a gradient of exactly zero
             slp, dist = ops.GamElboEmbed.apply(logits, task_var, xf, self.epsilon.view(-1), self._glm(), self.img_shape, self.grid_shape,
                                                self.convt5.bias)
         else:
@@ -632,8 +685,9 @@ class VAE(nn.Module):
                    sum_log_prob=slp, dist=dist, logits=logits, beta_mean=beta_mean, beta_cov=beta_cov,
                    gp_post=post)
         if want_maps:
-            emb = (self.img_shape, self.grid_shape) if self._embedded else (None, None)
-            out['maps'] = ops.gam_maps(logits.detach(), task_var.detach(), xf, self.epsilon.detach().view(-1), self._glm(), *emb)
+            emb = (self.img_shape, self.grid_shape) if (self._embedded or self.mask is not None) else (None, None)
+            out['maps'] = ops.gam_maps(logits.detach(), task_var.detach(), xf, self.epsilon.detach().view(-1), self._glm(), *emb,
+                                       mask=self.mask)
         return out
 
     def forward(self, ids, covariates, x, log_type, return_latent_rec=False, train_mode=True, noise=None):
@@ -855,6 +909,8 @@ class VAE(nn.Module):
             state['max_grad_norm'] = self.max_grad_norm
         if self.skip_nonfinite:
             state['skip_nonfinite'] = True
+        if self.mask is not None:                         # the brain mask, likewise: uint8, native shape
+            state['mask'] = self.mask.detach().clone()
         gp_out = {}
         for cov, d in self.gp_params.items():
             gp_out[cov] = {k: (torch.nn.Parameter(v.detach().clone()) if isinstance(v, torch.nn.Parameter) else v.clone())
@@ -892,6 +948,10 @@ class VAE(nn.Module):
         self._gain_const_cache.clear()
         self._graphs.clear()
         self._glm_f32 = None
+        # the mask the checkpointed run trained under is the one a resumed run / the export evaluates; a checkpoint without the key
+        # (the reference's, or a run without a mask) leaves the model's mask as constructed
+        if checkpoint.get('mask') is not None:
+            self.set_mask(checkpoint['mask'])
         # the guard the checkpointed run trained under; a checkpoint without the keys (the reference's, or a run without the guard)
         # loads with it off
         self.set_grad_guard(checkpoint.get('max_grad_norm'), bool(checkpoint.get('skip_nonfinite', False)))
