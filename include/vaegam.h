@@ -67,6 +67,30 @@ int vg_tconv3d_s2_stats(const vg_conv_desc* d, const float* x, const float* wpk,
                         const float* in_scale, const float* in_shift, float* y, int32_t stats_per_group,
                         int32_t stats_relu, double* stats_part, void* stream);
 
+/* What vg_corr3d / vg_tconv3d_s2 (stats_per_group > 0: vg_tconv3d_s2_stats) would launch for the descriptor: nothing is launched and no
+ * tensor memory is touched.  The record comes from the launchers' own planners, at the point where they would launch.
+ * has_prologue: the launch would be given in_scale / in_shift (d->relu_in is read from the descriptor); a mask_src changes no choice.
+ * out[0 .. VG_CONV_PLAN_LEN):
+ *    0 family (0 direct: corr3d_direct_k, 1 plane: corr3d_plane_k, 2 tconv: tconv3d_s2_k)
+ *    1 COT  2 KD  3 KH  4 KW  5 S  6 TDt  7 THt  8 TW  9 COC  10 NOPRO    the kernel instance (outputs per thread TDt x THt x TW x COT
+ *                                                                         channels; COC: compile-time CO, 0 = run-time; tconv: S 2, brick 2x2x2)
+ *   11 small                                                              the dispatcher's few-outputs switch
+ *   12 BW  13 BH  14 BD                                                   threads of a block along w / h / d (TWG, TH, TD; tconv: TJW, TJH, TJD)
+ *   15 tilesW  16 tilesH  17 tilesD                                       blocks per sample along w / h / d (plane: 1, nhb, tilesD)
+ *   18 threads  19 grid_x  20 grid_y  21 grid_z
+ *   plane only (else 0):
+ *   22 LD  23 CCH  24 chunks  25 nbuf                                     input planes staged per channel, channels per chunk, chunks, buffers
+ *   26 OHB  27 nhb  28 LH  29 lplane                                      output rows per row slab, slabs, staged input rows, LDS plane pitch
+ *   30 ch_floats  31 lds_bytes                                            LDS floats per channel slot, dynamic LDS of the block
+ *   tconv only (else 0):
+ *   32 JD  33 JH  34 JW                                                   2x2x2 bricks per dimension
+ *   35 stats_chunks                                                       vg_tconv3d_s2_stats_chunks(d, stats_per_group); 0 without statistics
+ * n_out < VG_CONV_PLAN_LEN returns VG_ERR_ARG; every descriptor the launcher refuses returns the launcher's status (VG_ERR_ARG,
+ * VG_ERR_UNSUPPORTED) with the same vg_last_error() text. */
+#define VG_CONV_PLAN_LEN 36
+int vg_corr3d_plan(const vg_conv_desc* d, int32_t has_prologue, int32_t* out, int32_t n_out);
+int vg_tconv3d_s2_plan(const vg_conv_desc* d, int32_t has_prologue, int32_t stats_per_group, int32_t* out, int32_t n_out);
+
 /* Table-driven implicit-GEMM convolution on the fp32 matrix cores (v_mfma_f32_16x16x4_f32, exact fp32): the forward passes and
  * data gradients of the conv / transposed-conv layers with 8 or 16 output channels (vae_reg_GP.py:189-215; replaces F.conv3d /
  * F.conv_transpose3d and their autograd data gradients, like vg_corr3d / vg_tconv3d_s2, for the launches that are real contractions).

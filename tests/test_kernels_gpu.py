@@ -1,6 +1,9 @@
 """HIP kernels (libvaegam_hip.so, through the C ABI) against plain PyTorch fp32 references on
 the GPU box: the shrunk per-layer cases of tests/kernel_cases.py plus every layer at the
-reference's real 41x49x35 geometry."""
+reference's real 41x49x35 geometry.  The real geometry is not the production launch: at the 2 or 4 samples
+these cases use, every 3x3x3 layer falls under the direct engine's `small` switch and runs the 4-channel
+instances, not the 8-wide plane-staged / transposed ones a training batch takes.  Those are pinned, class by
+class and against float64, by tests/conv_direct_cases.py (test_conv_direct_gpu.py)."""
 import numpy as np
 import pytest
 import torch
@@ -42,7 +45,8 @@ def test_first_layer_input_is_data():
     K.run_layer_case('cuda', name, spec, isz, with_bn=True, relu_in=False, groups=1, input_is_data=True, seed=5)
 
 
-# the reference's real layer geometry (vae_reg_GP.py:187-218)
+# the reference's real layer geometry (vae_reg_GP.py:187-218) -- at N = 2 (encoder) / 4 (decoder) samples, so the
+# 3x3x3 layers run the `small` 4-channel instances; the production instances and plan classes: tests/conv_direct_cases.py
 FULL = [(41, 49, 35), (39, 47, 33), (19, 23, 16), (17, 21, 14), (8, 10, 6), (6, 8, 5), (8, 10, 7), (16, 21, 14),
         (18, 23, 16), (39, 47, 33)]
 

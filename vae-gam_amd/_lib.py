@@ -64,6 +64,8 @@ _PROTOS = {
     'vg_tconv3d_s2': (ctypes.c_int, [ctypes.POINTER(ConvDesc), vp, vp, vp, vp, vp, vp, vp, vp]),
     'vg_tconv3d_s2_stats_chunks': (i64, [ctypes.POINTER(ConvDesc), i32]),
     'vg_tconv3d_s2_stats': (ctypes.c_int, [ctypes.POINTER(ConvDesc), vp, vp, vp, vp, vp, vp, i32, i32, vp, vp]),
+    'vg_corr3d_plan': (ctypes.c_int, [ctypes.POINTER(ConvDesc), i32, ctypes.POINTER(i32), i32]),
+    'vg_tconv3d_s2_plan': (ctypes.c_int, [ctypes.POINTER(ConvDesc), i32, i32, ctypes.POINTER(i32), i32]),
     'vg_bn_stats_from_parts': (ctypes.c_int, [vp, i32, i32, i64, f64, vp, vp, f32, vp, vp, vp, vp, vp, vp, vp]),
     'vg_wgrad3d_ws_bytes': (i64, [ctypes.POINTER(WgradDesc)]),
     'vg_wgrad3d': (ctypes.c_int, [ctypes.POINTER(WgradDesc), vp, vp, vp, vp, vp, vp, i32, vp]),
@@ -126,6 +128,10 @@ _PROTOS = {
 }
 WGRAD_PLAN_FIELDS = ('CA', 'KD', 'KH', 'KW', 'stride', 'PAD', 'DSH', 'PA', 'UG', 'RES', 'GRP', 'ONE', 'TPD', 'TPH', 'nbuf', 'pdblocks', 'nph',
                      'items', 'grid', 'wave_slabs', 'ipb', 'grp_items', 'nslabs', 'lds_bytes', 'blocks_per_cu')    # VG_WGRAD_PLAN_LEN, in order
+CONV_PLAN_FIELDS = ('family', 'COT', 'KD', 'KH', 'KW', 'S', 'TDt', 'THt', 'TW', 'COC', 'NOPRO', 'small', 'BW', 'BH', 'BD', 'tilesW', 'tilesH',
+                    'tilesD', 'threads', 'grid_x', 'grid_y', 'grid_z', 'LD', 'CCH', 'chunks', 'nbuf', 'OHB', 'nhb', 'LH', 'lplane', 'ch_floats',
+                    'lds_bytes', 'JD', 'JH', 'JW', 'stats_chunks')                                           # VG_CONV_PLAN_LEN, in order
+CONV_FAMILIES = ('direct', 'plane', 'tconv')                                                                # values of field 0
 GUARD_STATE_LEN = 8            # VG_GUARD_STATE_LEN: [total_norm, scale, apply, seen, skipped, clipped, norm_sum, norm_max]
 EXPORTS = tuple(_PROTOS)
 

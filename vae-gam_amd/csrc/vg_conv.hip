@@ -33,6 +33,12 @@ struct CorrParams {
 
 __device__ __forceinline__ int clampi(int v, int lo, int hi) { return min(max(v, lo), hi); }
 
+// What a query call (no launch) wants back from a launcher, at the point where it would launch: the record of vg_corr3d_plan /
+// vg_tconv3d_s2_plan (include/vaegam.h), the statistics chunk count of vg_tconv3d_s2_stats_chunks, or both.  `small` is the
+// dispatcher's switch, handed through for the record.
+struct ConvQuery { int32_t* plan; int64_t* chunks; int small; };
+enum { FAM_DIRECT = 0, FAM_PLANE = 1, FAM_TCONV = 2 };
+
 // ------------------------------------------------------------------------------------------
 // corr3d
 // ------------------------------------------------------------------------------------------
@@ -207,7 +213,7 @@ corr3d_direct_k(const float* __restrict__ x, const float* __restrict__ wpk, cons
 
 template <int COT, int KD, int KH, int KW, int S, int TDt, int THt, int TW, int COC = 0>
 int launch_corr(const vg_conv_desc* d, const float* x, const float* wpk, const float* bias, const float* in_scale,
-                const float* in_shift, const float* mask_src, float* y, hipStream_t s) {
+                const float* in_shift, const float* mask_src, float* y, hipStream_t s, const ConvQuery* query = nullptr) {
     CorrParams p; p.d = *d;
     const int gw = vg_cdiv(d->OW, TW), gh = vg_cdiv(d->OH, THt), gd = vg_cdiv(d->OD, TDt);
     // a block covers a compact brick of outputs so that the overlapping input windows of its
@@ -223,6 +229,15 @@ int launch_corr(const vg_conv_desc* d, const float* x, const float* wpk, const f
     if (d->CO % COT) { vg_set_error("corr3d: CO=%d not a multiple of %d", d->CO, COT); return VG_ERR_UNSUPPORTED; }
     const int threads = vg_cdiv(p.TWG * p.TH * p.TD, VG_WAVE) * VG_WAVE;
     dim3 grid(p.tilesW * p.tilesH * p.tilesD, d->N, d->CO / COT);
+    if (query) {                                            // nothing is launched: the choices the launch below would use
+        if (query->plan) {
+            const int32_t rec[VG_CONV_PLAN_LEN] = {
+                FAM_DIRECT, COT, KD, KH, KW, S, TDt, THt, TW, COC, 0, query->small, p.TWG, p.TH, p.TD, p.tilesW, p.tilesH, p.tilesD,
+                threads, (int32_t)grid.x, (int32_t)grid.y, (int32_t)grid.z};
+            for (int i = 0; i < VG_CONV_PLAN_LEN; ++i) query->plan[i] = rec[i];
+        }
+        return VG_OK;
+    }
     vg_launch(corr3d_direct_k<COT, KD, KH, KW, S, TDt, THt, TW, COC>, grid, dim3(threads), 0, s,
               x, wpk, bias, in_scale, in_shift, mask_src, y, p);
     return vg_check_launch("corr3d_direct");
@@ -484,7 +499,7 @@ corr3d_plane_k(const float* __restrict__ x, const float* __restrict__ wpk, const
 // plane-staged launch; returns -1 if the geometry does not fit (caller falls back to the direct kernel)
 template <int COT, int KD, int KH, int KW, int S, int TDt, int THt, int TW, int COC = 0>
 int launch_corr_plane(const vg_conv_desc* d, const float* x, const float* wpk, const float* bias, const float* in_scale,
-                      const float* in_shift, const float* mask_src, float* y, hipStream_t s) {
+                      const float* in_shift, const float* mask_src, float* y, hipStream_t s, const ConvQuery* query = nullptr) {
     CorrPlaneParams p; p.d = *d;
     const int gw = vg_cdiv(d->OW, TW), gd = vg_cdiv(d->OD, TDt);
     if (gw > 256) return -1;
@@ -535,8 +550,19 @@ int launch_corr_plane(const vg_conv_desc* d, const float* x, const float* wpk, c
     if (d->CO % COT) { vg_set_error("corr3d: CO=%d not a multiple of %d", d->CO, COT); return VG_ERR_UNSUPPORTED; }
     const int threads = vg_cdiv(p.TWG * p.TH * p.TD, VG_WAVE) * VG_WAVE;
     dim3 grid(p.tilesD * p.nhb, d->N, d->CO / COT);
+    const bool nopro = KD == 5 && in_scale == nullptr && !d->relu_in;
+    if (query) {                                            // nothing is launched: the choices the launches below would use
+        if (query->plan) {
+            const int32_t rec[VG_CONV_PLAN_LEN] = {
+                FAM_PLANE, COT, KD, KH, KW, S, TDt, THt, TW, COC, nopro ? 1 : 0, query->small, p.TWG, p.TH, p.TD, 1, p.nhb, p.tilesD,
+                threads, (int32_t)grid.x, (int32_t)grid.y, (int32_t)grid.z,
+                p.LD, p.CCH, vg_cdiv(d->CI, p.CCH), p.nbuf, p.OHB, p.nhb, p.LH, p.lplane, p.ch_floats, (int32_t)shmem};
+            for (int i = 0; i < VG_CONV_PLAN_LEN; ++i) query->plan[i] = rec[i];
+        }
+        return VG_OK;
+    }
     if constexpr (KD == 5) {                                     // (the instances built with vector masks; the one-channel one always has a prologue)
-        if (in_scale == nullptr && !d->relu_in) {
+        if (nopro) {
             vg_launch(corr3d_plane_k<COT, KD, KH, KW, S, TDt, THt, TW, COC, true>, grid, dim3(threads), shmem, s,
                       x, wpk, bias, in_scale, in_shift, mask_src, y, p);
             return vg_check_launch("corr3d_plane");
@@ -752,7 +778,7 @@ tconv3d_s2_k(const float* __restrict__ x, const float* __restrict__ wpk, const f
 template <int COT, int KD, int KH, int KW, int COC = 0>
 int launch_tconv(const vg_conv_desc* d, const float* x, const float* wpk, const float* bias, const float* in_scale,
                  const float* in_shift, const float* mask_src, float* y, hipStream_t s,
-                 double* stats_part = nullptr, int stats_relu = 0, int stats_pg = 1, int64_t* chunks_only = nullptr) {
+                 double* stats_part = nullptr, int stats_relu = 0, int stats_pg = 1, const ConvQuery* query = nullptr) {
     TconvParams p; p.d = *d;
     p.JD = (d->OD + d->pad_d + 1) / 2; p.JH = (d->OH + d->pad_h + 1) / 2; p.JW = (d->OW + d->pad_w + 1) / 2;
     p.TJW = p.JW < 32 ? p.JW : 32;
@@ -765,8 +791,19 @@ int launch_tconv(const vg_conv_desc* d, const float* x, const float* wpk, const 
     if (d->CO % COT) { vg_set_error("tconv3d_s2: CO=%d not a multiple of %d", d->CO, COT); return VG_ERR_UNSUPPORTED; }
     const int threads = vg_cdiv(p.TJW * p.TJH * p.TJD, VG_WAVE) * VG_WAVE;
     dim3 grid(p.tilesW * p.tilesH * p.tilesD, d->N, d->CO / COT);
-    if (chunks_only) { *chunks_only = (int64_t)stats_pg * grid.x * (threads / VG_WAVE); return VG_OK; }
-    if (in_scale == nullptr && !d->relu_in)
+    const bool nopro = in_scale == nullptr && !d->relu_in;
+    if (query) {                                            // nothing is launched: the choices the launches below would use
+        const int64_t chunks = (int64_t)stats_pg * grid.x * (threads / VG_WAVE);
+        if (query->chunks) *query->chunks = chunks;
+        if (query->plan) {
+            const int32_t rec[VG_CONV_PLAN_LEN] = {
+                FAM_TCONV, COT, KD, KH, KW, 2, 2, 2, 2, COC, nopro ? 1 : 0, query->small, p.TJW, p.TJH, p.TJD, p.tilesW, p.tilesH, p.tilesD,
+                threads, (int32_t)grid.x, (int32_t)grid.y, (int32_t)grid.z, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, p.JD, p.JH, p.JW, (int32_t)chunks};
+            for (int i = 0; i < VG_CONV_PLAN_LEN; ++i) query->plan[i] = rec[i];
+        }
+        return VG_OK;
+    }
+    if (nopro)
         vg_launch(tconv3d_s2_k<COT, KD, KH, KW, COC, true>, grid, dim3(threads), 0, s,
                   x, wpk, bias, in_scale, in_shift, mask_src, y, p, stats_part, stats_relu, stats_pg);
     else
@@ -789,8 +826,9 @@ static int check_desc(const vg_conv_desc* d, const void* x, const void* w, const
     return VG_OK;
 }
 
-extern "C" int vg_corr3d(const vg_conv_desc* d, const float* x, const float* wpk, const float* bias,
-                         const float* in_scale, const float* in_shift, const float* mask_src, float* y, void* stream) {
+// vg_corr3d and its plan query: one path through the checks, the instance table and the launchers' planners (query: no launch)
+static int corr_dispatch(const vg_conv_desc* d, const float* x, const float* wpk, const float* bias, const float* in_scale,
+                         const float* in_shift, const float* mask_src, float* y, hipStream_t s, ConvQuery* query) {
     int rc = check_desc(d, x, wpk, y, "vg_corr3d");
     if (rc) return rc;
     if ((in_scale == nullptr) != (in_shift == nullptr) || (in_scale && d->per_group <= 0)) {
@@ -804,25 +842,25 @@ extern "C" int vg_corr3d(const vg_conv_desc* d, const float* x, const float* wpk
         vg_set_error("vg_corr3d: output %dx%dx%d inconsistent with input %dx%dx%d", d->OD, d->OH, d->OW, d->ID, d->IH, d->IW);
         return VG_ERR_ARG;
     }
-    hipStream_t s = (hipStream_t)stream;
     // "small" launches (few output positions) trade register tiling for parallelism: fewer outputs and
     // fewer output channels per thread, the channel groups spread over grid.z
     const long long pos = (long long)d->N * d->OD * d->OH * d->OW;
     const bool small = pos * d->CO < (long long)1536 * 1024;
     const bool k333 = d->KD == 3 && d->KH == 3 && d->KW == 3;
+    if (query) query->small = small ? 1 : 0;
 #define CORR(COT, KD, KH, KW, S, TDt, THt, TW) \
-    return launch_corr<COT, KD, KH, KW, S, TDt, THt, TW>(d, x, wpk, bias, in_scale, in_shift, mask_src, y, s)
+    return launch_corr<COT, KD, KH, KW, S, TDt, THt, TW>(d, x, wpk, bias, in_scale, in_shift, mask_src, y, s, query)
 #define CORR_LDS(COT, KD, KH, KW, S, TDt, THt, TW) \
-    { int r_ = d->CO == COT ? launch_corr_plane<COT, KD, KH, KW, S, TDt, THt, TW, COT>(d, x, wpk, bias, in_scale, in_shift, mask_src, y, s) \
-             : d->CO == 2 * COT ? launch_corr_plane<COT, KD, KH, KW, S, TDt, THt, TW, 2 * COT>(d, x, wpk, bias, in_scale, in_shift, mask_src, y, s) \
-             : launch_corr_plane<COT, KD, KH, KW, S, TDt, THt, TW, 0>(d, x, wpk, bias, in_scale, in_shift, mask_src, y, s); \
+    { int r_ = d->CO == COT ? launch_corr_plane<COT, KD, KH, KW, S, TDt, THt, TW, COT>(d, x, wpk, bias, in_scale, in_shift, mask_src, y, s, query) \
+             : d->CO == 2 * COT ? launch_corr_plane<COT, KD, KH, KW, S, TDt, THt, TW, 2 * COT>(d, x, wpk, bias, in_scale, in_shift, mask_src, y, s, query) \
+             : launch_corr_plane<COT, KD, KH, KW, S, TDt, THt, TW, 0>(d, x, wpk, bias, in_scale, in_shift, mask_src, y, s, query); \
       if (r_ >= 0) return r_; \
-      return launch_corr<COT, KD, KH, KW, S, TDt, THt, TW>(d, x, wpk, bias, in_scale, in_shift, mask_src, y, s); }
+      return launch_corr<COT, KD, KH, KW, S, TDt, THt, TW>(d, x, wpk, bias, in_scale, in_shift, mask_src, y, s, query); }
 #define CORR_LDS_RT(COT, KD, KH, KW, S, TDt, THt, TW) /* run-time channel count: measured faster for the 3x3x3 stride-1 8-wide instance */ \
-    { int r_ = launch_corr_plane<COT, KD, KH, KW, S, TDt, THt, TW, 0>(d, x, wpk, bias, in_scale, in_shift, mask_src, y, s); \
+    { int r_ = launch_corr_plane<COT, KD, KH, KW, S, TDt, THt, TW, 0>(d, x, wpk, bias, in_scale, in_shift, mask_src, y, s, query); \
       if (r_ >= 0) return r_; \
-      if (d->CO == COT) return launch_corr<COT, KD, KH, KW, S, TDt, THt, TW, COT>(d, x, wpk, bias, in_scale, in_shift, mask_src, y, s); \
-      return launch_corr<COT, KD, KH, KW, S, TDt, THt, TW>(d, x, wpk, bias, in_scale, in_shift, mask_src, y, s); }
+      if (d->CO == COT) return launch_corr<COT, KD, KH, KW, S, TDt, THt, TW, COT>(d, x, wpk, bias, in_scale, in_shift, mask_src, y, s, query); \
+      return launch_corr<COT, KD, KH, KW, S, TDt, THt, TW>(d, x, wpk, bias, in_scale, in_shift, mask_src, y, s, query); }
     if (k333 && d->stride == 1) {
         // one output channel (the decoder's last layer): 4x2x4 outputs per thread, 6 input planes per 4 output planes (input fetched
         // 1.5x instead of 2x), two blocks per CU with the next channel's planes in flight: 803 -> 735 us at batch 64 / 8 covariates
@@ -838,19 +876,34 @@ extern "C" int vg_corr3d(const vg_conv_desc* d, const float* x, const float* wpk
     if (d->KD == 4 && d->KH == 4 && d->KW == 4 && d->stride == 2 && d->CO % 8 == 0) CORR_LDS(8, 4, 4, 4, 2, 1, 1, 4);
 #undef CORR
 #undef CORR_LDS
+#undef CORR_LDS_RT
     vg_set_error("vg_corr3d: no kernel instance for CO=%d k=%dx%dx%d stride=%d", d->CO, d->KD, d->KH, d->KW, d->stride);
     return VG_ERR_UNSUPPORTED;
 }
 
+extern "C" int vg_corr3d(const vg_conv_desc* d, const float* x, const float* wpk, const float* bias,
+                         const float* in_scale, const float* in_shift, const float* mask_src, float* y, void* stream) {
+    return corr_dispatch(d, x, wpk, bias, in_scale, in_shift, mask_src, y, (hipStream_t)stream, nullptr);
+}
+
+extern "C" int vg_corr3d_plan(const vg_conv_desc* d, int32_t has_prologue, int32_t* out, int32_t n_out) {
+    if (!out || n_out < VG_CONV_PLAN_LEN) { vg_set_error("vg_corr3d_plan: out must hold VG_CONV_PLAN_LEN values"); return VG_ERR_ARG; }
+    float dummy;                                            // stands for every tensor: the checks want non-null pointers, nothing reads them
+    const float* pro = has_prologue ? &dummy : nullptr;
+    ConvQuery q = {out, nullptr, 0};
+    return corr_dispatch(d, &dummy, &dummy, nullptr, pro, pro, nullptr, &dummy, nullptr, &q);
+}
+
 static int tconv_dispatch(const vg_conv_desc* d, const float* x, const float* wpk, const float* bias, const float* in_scale,
                           const float* in_shift, const float* mask_src, float* y, hipStream_t s,
-                          double* stats_part, int stats_relu, int stats_pg, int64_t* chunks_only) {
+                          double* stats_part, int stats_relu, int stats_pg, ConvQuery* query) {
     const long long pos = (long long)d->N * d->OD * d->OH * d->OW;
     const bool small = pos * d->CO < (long long)8 * 1024 * 1024;
+    if (query) query->small = small ? 1 : 0;
 #define TCONV(COT, KD, KH, KW) \
-    { if (d->CO == 8) return launch_tconv<COT, KD, KH, KW, 8>(d, x, wpk, bias, in_scale, in_shift, mask_src, y, s, stats_part, stats_relu, stats_pg, chunks_only); \
-      if (d->CO == 16) return launch_tconv<COT, KD, KH, KW, 16>(d, x, wpk, bias, in_scale, in_shift, mask_src, y, s, stats_part, stats_relu, stats_pg, chunks_only); \
-      return launch_tconv<COT, KD, KH, KW, 0>(d, x, wpk, bias, in_scale, in_shift, mask_src, y, s, stats_part, stats_relu, stats_pg, chunks_only); }
+    { if (d->CO == 8) return launch_tconv<COT, KD, KH, KW, 8>(d, x, wpk, bias, in_scale, in_shift, mask_src, y, s, stats_part, stats_relu, stats_pg, query); \
+      if (d->CO == 16) return launch_tconv<COT, KD, KH, KW, 16>(d, x, wpk, bias, in_scale, in_shift, mask_src, y, s, stats_part, stats_relu, stats_pg, query); \
+      return launch_tconv<COT, KD, KH, KW, 0>(d, x, wpk, bias, in_scale, in_shift, mask_src, y, s, stats_part, stats_relu, stats_pg, query); }
     if (d->KD == 3 && d->KH == 3 && d->KW == 3) {
         if (d->CO % 8 == 0 && !small) TCONV(8, 3, 3, 3);
         if (d->CO % 4 == 0 && small) TCONV(4, 3, 3, 3);
@@ -884,8 +937,24 @@ extern "C" int64_t vg_tconv3d_s2_stats_chunks(const vg_conv_desc* d, int32_t sta
     if (!d || stats_per_group <= 0 || d->N % stats_per_group) return -1;
     int64_t chunks = 0;
     float dummy;
-    int rc = tconv_dispatch(d, &dummy, &dummy, nullptr, nullptr, nullptr, nullptr, &dummy, nullptr, nullptr, 0, stats_per_group, &chunks);
+    ConvQuery q = {nullptr, &chunks, 0};
+    int rc = tconv_dispatch(d, &dummy, &dummy, nullptr, nullptr, nullptr, nullptr, &dummy, nullptr, nullptr, 0, stats_per_group, &q);
     return rc ? -1 : chunks;
+}
+
+extern "C" int vg_tconv3d_s2_plan(const vg_conv_desc* d, int32_t has_prologue, int32_t stats_per_group, int32_t* out, int32_t n_out) {
+    if (!out || n_out < VG_CONV_PLAN_LEN) { vg_set_error("vg_tconv3d_s2_plan: out must hold VG_CONV_PLAN_LEN values"); return VG_ERR_ARG; }
+    float dummy;
+    const float* pro = has_prologue ? &dummy : nullptr;
+    int rc = tconv_check(d, &dummy, &dummy, pro, pro, &dummy);
+    if (rc) return rc;
+    if (stats_per_group < 0 || (stats_per_group > 0 && d->N % stats_per_group)) {           // as vg_tconv3d_s2_stats
+        vg_set_error("vg_tconv3d_s2_plan: bad statistics arguments"); return VG_ERR_ARG;
+    }
+    ConvQuery q = {out, nullptr, 0};
+    rc = tconv_dispatch(d, &dummy, &dummy, nullptr, pro, pro, nullptr, &dummy, nullptr, nullptr, 0, stats_per_group > 0 ? stats_per_group : 1, &q);
+    if (rc == VG_OK && stats_per_group <= 0) out[VG_CONV_PLAN_LEN - 1] = 0;                  // no statistics: no chunks
+    return rc;
 }
 
 extern "C" int vg_tconv3d_s2_stats(const vg_conv_desc* d, const float* x, const float* wpk, const float* bias,

@@ -247,6 +247,54 @@ def _conv_desc(N, ci, co, isz, osz, k, stride, pad, relu_in, per_group, relu_out
                     pad[0], pad[1], pad[2], int(relu_in), int(per_group), int(bool(relu_out)))
 
 
+def conv_fwd_desc(spec: ConvSpec, N, isz, relu_in=False, per_group=1, relu_out=False):
+    """-> (entry point, vg_conv_desc, output size) of a layer's forward launch on the register-tiled engine (vg_conv.hip): a Conv3d
+    and a stride-1 ConvTranspose3d are correlations (the latter padded by k - 1 - pad), a stride-2 ConvTranspose3d runs in gather form."""
+    isz = tuple(int(v) for v in isz); osz = spec.out_size(isz)
+    if spec.kind == 'conv':
+        assert spec.pad == (0, 0, 0)
+        return 'vg_corr3d', _conv_desc(N, spec.ci, spec.co, isz, osz, spec.k, spec.stride, (0, 0, 0), relu_in, per_group, relu_out), osz
+    if spec.stride == 1:
+        padc = tuple(spec.k[a] - 1 - spec.pad[a] for a in range(3))
+        return 'vg_corr3d', _conv_desc(N, spec.ci, spec.co, isz, osz, spec.k, 1, padc, relu_in, per_group, relu_out), osz
+    return 'vg_tconv3d_s2', _conv_desc(N, spec.ci, spec.co, isz, osz, spec.k, 2, spec.pad, relu_in, per_group, relu_out), osz
+
+
+def conv_bwd_desc(spec: ConvSpec, N, osz, isz):
+    """-> (entry point, vg_conv_desc) of a layer's data-gradient launch: reads dy (the layer's output size osz), writes dx (isz)."""
+    osz = tuple(int(v) for v in osz); isz = tuple(int(v) for v in isz)
+    if spec.kind == 'convt':
+        # dx[i] = sum_k dy[i*s - pad + k] w[k]: strided correlation over dy
+        return 'vg_corr3d', _conv_desc(N, spec.co, spec.ci, osz, isz, spec.k, spec.stride, spec.pad, False, 1)
+    if spec.stride == 1:
+        padc = tuple(spec.k[a] - 1 for a in range(3))
+        return 'vg_corr3d', _conv_desc(N, spec.co, spec.ci, osz, isz, spec.k, 1, padc, False, 1)
+    return 'vg_tconv3d_s2', _conv_desc(N, spec.co, spec.ci, osz, isz, spec.k, 2, (0, 0, 0), False, 1)
+
+
+ConvPlan = namedtuple('ConvPlan', _lib.CONV_PLAN_FIELDS)
+
+
+def conv_plan(spec: ConvSpec, direction: str, N, isz, relu_in=False, has_prologue=False, per_group=1, next_bn=None) -> ConvPlan:
+    """What conv_forward (direction 'fwd') / conv_backward_data ('bwd') would launch on the register-tiled engine for a layer with
+    input size isz and N samples, from the launchers' own planners (vg_corr3d_plan / vg_tconv3d_s2_plan): nothing is launched,
+    shapes only.  has_prologue: the forward is given scale / shift; next_bn as conv_forward.  `family` is 'direct', 'plane' or 'tconv'."""
+    isz = tuple(int(v) for v in isz)
+    if direction == 'fwd':
+        fn, d, _ = conv_fwd_desc(spec, int(N), isz, relu_in, per_group)
+    else:
+        assert direction == 'bwd' and not has_prologue and not next_bn
+        fn, d = conv_bwd_desc(spec, int(N), spec.out_size(isz), isz)
+    rec = (ctypes.c_int32 * len(ConvPlan._fields))()
+    if fn == 'vg_corr3d':
+        if next_bn:
+            raise ValueError('next_bn: only the stride-2 transposed-conv kernel accumulates the next layer\'s statistics')
+        _lib.get_lib().call('vg_corr3d_plan', ctypes.byref(d), int(bool(has_prologue)), rec, len(rec))
+    else:
+        _lib.get_lib().call('vg_tconv3d_s2_plan', ctypes.byref(d), int(bool(has_prologue)), int(next_bn or 0), rec, len(rec))
+    return ConvPlan(_lib.CONV_FAMILIES[rec[0]], *rec[1:])
+
+
 def conv_forward(x, wpk, bias, spec: ConvSpec, relu_in=False, scale=None, shift=None, per_group=1, next_bn=None, relu_out=False):
     """Layer forward: y = conv/convT(P(x)) + bias, y is the pre-activation -- or, with relu_out, max(y, 0) (the rectified hand-off
     of BnConvAct; the statistics partials of next_bn are the same either way).
@@ -255,28 +303,17 @@ def conv_forward(x, wpk, bias, spec: ConvSpec, relu_in=False, scale=None, shift=
     partials to the consuming layer's bn_stats(pre=...) explicitly."""
     lib = _lib.get_lib()
     N = x.shape[0]
-    isz = tuple(x.shape[2:]); osz = spec.out_size(isz)
+    fn, d, osz = conv_fwd_desc(spec, N, tuple(x.shape[2:]), relu_in, per_group, relu_out)
     y = torch.empty((N, spec.co) + osz, dtype=torch.float32, device=x.device)
     _chk(x); _chk(wpk)
-    if spec.kind == 'conv':
-        assert spec.pad == (0, 0, 0)
-        d = _conv_desc(N, spec.ci, spec.co, isz, osz, spec.k, spec.stride, (0, 0, 0), relu_in, per_group, relu_out)
-        _call(x, 'vg_corr3d', ctypes.byref(d), _p(x), _p(wpk), _p(bias), _p(scale), _p(shift), None, _p(y))
-    elif spec.stride == 1:
-        padc = tuple(spec.k[a] - 1 - spec.pad[a] for a in range(3))
-        d = _conv_desc(N, spec.ci, spec.co, isz, osz, spec.k, 1, padc, relu_in, per_group, relu_out)
-        _call(x, 'vg_corr3d', ctypes.byref(d), _p(x), _p(wpk), _p(bias), _p(scale), _p(shift), None, _p(y))
-    else:
-        d = _conv_desc(N, spec.ci, spec.co, isz, osz, spec.k, 2, spec.pad, relu_in, per_group, relu_out)
-        if next_bn:
-            chunks = lib.size('vg_tconv3d_s2_stats_chunks', ctypes.byref(d), int(next_bn))
-            G = N // int(next_bn)
-            part = torch.empty(G * spec.co * chunks * 2, dtype=torch.float64, device=x.device)
-            _call(x, 'vg_tconv3d_s2_stats', ctypes.byref(d), _p(x), _p(wpk), _p(bias), _p(scale), _p(shift), _p(y), int(next_bn), 1,
-                     _p(part))
-            return y, part
-        else:
-            _call(x, 'vg_tconv3d_s2', ctypes.byref(d), _p(x), _p(wpk), _p(bias), _p(scale), _p(shift), None, _p(y))
+    if fn == 'vg_tconv3d_s2' and next_bn:
+        chunks = lib.size('vg_tconv3d_s2_stats_chunks', ctypes.byref(d), int(next_bn))
+        G = N // int(next_bn)
+        part = torch.empty(G * spec.co * chunks * 2, dtype=torch.float64, device=x.device)
+        _call(x, 'vg_tconv3d_s2_stats', ctypes.byref(d), _p(x), _p(wpk), _p(bias), _p(scale), _p(shift), _p(y), int(next_bn), 1,
+                 _p(part))
+        return y, part
+    _call(x, fn, ctypes.byref(d), _p(x), _p(wpk), _p(bias), _p(scale), _p(shift), None, _p(y))
     if next_bn:
         raise ValueError('next_bn: only the stride-2 transposed-conv kernel accumulates the next layer\'s statistics')
     return y
@@ -284,22 +321,12 @@ def conv_forward(x, wpk, bias, spec: ConvSpec, relu_in=False, scale=None, shift=
 
 def conv_backward_data(dy, wpk_bwd, spec: ConvSpec, in_size, mask_src=None):
     """Gradient w.r.t. the layer's (post-prologue) input; `mask_src` fuses the producer's ReLU backward."""
-    lib = _lib.get_lib()
     N = dy.shape[0]
-    osz = tuple(dy.shape[2:]); isz = tuple(in_size)
+    isz = tuple(in_size)
+    fn, d = conv_bwd_desc(spec, N, tuple(dy.shape[2:]), isz)
     dx = torch.empty((N, spec.ci) + isz, dtype=torch.float32, device=dy.device)
     _chk(dy); _chk(wpk_bwd)
-    if spec.kind == 'convt':
-        # dx[i] = sum_k dy[i*s - pad + k] w[k]: strided correlation over dy
-        d = _conv_desc(N, spec.co, spec.ci, osz, isz, spec.k, spec.stride, spec.pad, False, 1)
-        _call(dy, 'vg_corr3d', ctypes.byref(d), _p(dy), _p(wpk_bwd), None, None, None, _p(mask_src), _p(dx))
-    elif spec.stride == 1:
-        padc = tuple(spec.k[a] - 1 for a in range(3))
-        d = _conv_desc(N, spec.co, spec.ci, osz, isz, spec.k, 1, padc, False, 1)
-        _call(dy, 'vg_corr3d', ctypes.byref(d), _p(dy), _p(wpk_bwd), None, None, None, _p(mask_src), _p(dx))
-    else:
-        d = _conv_desc(N, spec.co, spec.ci, osz, isz, spec.k, 2, (0, 0, 0), False, 1)
-        _call(dy, 'vg_tconv3d_s2', ctypes.byref(d), _p(dy), _p(wpk_bwd), None, None, None, _p(mask_src), _p(dx))
+    _call(dy, fn, ctypes.byref(d), _p(dy), _p(wpk_bwd), None, None, None, _p(mask_src), _p(dx))
     return dx
 
 
