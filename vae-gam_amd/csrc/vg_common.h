@@ -229,6 +229,35 @@ __device__ __forceinline__ void vg_mfma16(float a, float b, vg_f32x4& acc) {
 struct __attribute__((packed, aligned(4))) vg_f2u { float a, b; };
 __device__ __forceinline__ void vg_store2(float* p, float a, float b) { vg_f2u v; v.a = a; v.b = b; *reinterpret_cast<vg_f2u*>(p) = v; }
 
+// One dword at (wave-uniform base) + (32-bit per-lane byte offset): written through a global-address-space pointer with the offset
+// zero-extended right at the access, which the compiler selects as `global_store_dword voff, vdata, s[base:base+1]` (a generic pointer
+// whose 64-bit per-lane form was computed elsewhere costs a v_lshl_add_u64 per access instead).
+#ifdef VG_EMU
+static inline void vg_store_sbase(float* base, unsigned off, float v) { *reinterpret_cast<float*>(reinterpret_cast<char*>(base) + off) = v; }
+static inline float vg_load_sbase(const float* base, unsigned off) { return *reinterpret_cast<const float*>(reinterpret_cast<const char*>(base) + off); }
+#else
+__device__ __forceinline__ void vg_store_sbase(float* base, unsigned off, float v) {
+    typedef __attribute__((address_space(1))) char* gptr;
+    *(__attribute__((address_space(1))) float*)((gptr)base + off) = v;
+}
+__device__ __forceinline__ float vg_load_sbase(const float* base, unsigned off) {
+    typedef const __attribute__((address_space(1))) char* gptr;
+    return *(const __attribute__((address_space(1))) float*)((gptr)base + off);
+}
+#endif
+
+// Two floats in a register pair: + and fma on it are v_pk_add_f32 / v_pk_fma_f32 (gfx950), per element the same IEEE operation as the
+// scalar form.
+#ifdef VG_EMU
+struct vg_f2 { float x, y; };
+static inline vg_f2 vg_pk_add(vg_f2 a, vg_f2 b) { vg_f2 r; r.x = a.x + b.x; r.y = a.y + b.y; return r; }
+static inline vg_f2 vg_pk_fma(vg_f2 a, vg_f2 b, vg_f2 c) { vg_f2 r; r.x = fmaf(a.x, b.x, c.x); r.y = fmaf(a.y, b.y, c.y); return r; }
+#else
+typedef float vg_f2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ vg_f2 vg_pk_add(vg_f2 a, vg_f2 b) { return a + b; }
+__device__ __forceinline__ vg_f2 vg_pk_fma(vg_f2 a, vg_f2 b, vg_f2 c) { return __builtin_elementwise_fma(a, b, c); }
+#endif
+
 // Sum over the 64 lanes of a wave, returned in every lane.  On the GPU: six DPP adds inside the vector ALU (row shifts 1, 2, 4, 8, then
 // the two row broadcasts; the total lands in lane 63 and is read back as a scalar) instead of six ds_bpermute round trips through the
 // LDS pipe per __shfl_down reduction -- the fused GAM/ELBO backward does 8 of them per sample and wave.
@@ -258,6 +287,14 @@ static inline unsigned vg_opaque(unsigned v) { return v; }
 #else
 __device__ __forceinline__ float vg_opaque(float v) { asm volatile("" : "+v"(v)); return v; }
 __device__ __forceinline__ unsigned vg_opaque(unsigned v) { asm volatile("" : "+v"(v)); return v; }
+#endif
+
+// marks a register value as redefined (no instruction): what is computed from it afterwards is computed there, not hoisted out of the
+// enclosing loop and kept in further registers
+#ifdef VG_EMU
+static inline void vg_touch(unsigned&) {}
+#else
+__device__ __forceinline__ void vg_touch(unsigned& v) { asm volatile("" : "+v"(v)); }
 #endif
 
 // value with its bits and-ed by an all-ones / all-zero mask: an exact select that keeps its condition in a VECTOR register

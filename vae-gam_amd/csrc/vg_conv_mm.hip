@@ -20,6 +20,7 @@
 #include "vg_common.h"
 #include <stdlib.h>
 #include <stdint.h>
+#include <type_traits>
 #include "../../include/vaegam.h"
 
 #ifdef VG_STAMP
@@ -137,9 +138,9 @@ conv_mm_k(const float* __restrict__ x, const float* __restrict__ a_img, const in
     // pw*swi + dw) of the staged planes, or, where that element does not exist (zero padding, tile overhang, lanes past the last
     // position), the slot's zero pad.  Float offsets from the slot base; with compile-time step counts they live in registers
     // (pt), so a matrix instruction costs one address add + one ds_read_b32 and no select.
-    // Per tile: ob = offset of the lane's first output element of class 0 inside the sample (channel co_l, replica rho_l); bit
+    // Per tile: ob = BYTE offset of the lane's first output element of class 0 inside the sample (channel co_l, replica rho_l); bit
     // q*TPC + i of vbits = "tile i of class q writes an element that exists".
-    int ob[TPC];
+    unsigned ob[TPC];
     unsigned vbits = 0;
     int pt[TPC][STATIC_K ? KSUM : 1];
     int posBase[TPC]; unsigned vm[NQ][TPC];                              // run-time step counts only
@@ -152,7 +153,7 @@ conv_mm_k(const float* __restrict__ x, const float* __restrict__ a_img, const in
         const int phl = r2 / d.PW, pw = r2 - phl * d.PW;
         const int ph = ph0 + phl;
         const int obd = (pd0 + pdl) * d.sdo, obh = ph * d.sho, obw = pw * d.swo + rho_l;
-        ob[i] = obd * OHW + obh * d.OW + obw + co_l * (int)ovol;
+        ob[i] = 4u * (unsigned)(obd * OHW + obh * d.OW + obw + co_l * (int)ovol);
 #pragma unroll
         for (int q = 0; q < NQ; ++q) {
             const int od = obd + d.od0[q], oh = obh + d.oh0[q], ow = obw + d.ow0[q];
@@ -188,15 +189,18 @@ conv_mm_k(const float* __restrict__ x, const float* __restrict__ a_img, const in
     const int nsamp = (d.N - split + p.nsplit - 1) / p.nsplit;          // samples this block visits: split, split + nsplit, ...
     const int units = nsamp * nchunks;
 
-    vg_f32x4 acc[TPC];
-    float st_s[4] = {0.f, 0.f, 0.f, 0.f}, st_q[4] = {0.f, 0.f, 0.f, 0.f};
-    float mreg[MASKED ? TPC : 1][4];                                     // ReLU mask source of the sample in flight (data gradients)
-    float bias_l[4];
+    vg_f32x4 acc[TPC];                                                   // zero in front of a class's first matrix instruction: store_class leaves them so
 #pragma unroll
-    for (int r = 0; r < 4; ++r) bias_l[r] = bias ? bias[co_l + r] : 0.f;
+    for (int i = 0; i < TPC; ++i) { acc[i].v[0] = 0.f; acc[i].v[1] = 0.f; acc[i].v[2] = 0.f; acc[i].v[3] = 0.f; }
+    vg_f2 st_s[2] = {{0.f, 0.f}, {0.f, 0.f}}, st_q[2] = {{0.f, 0.f}, {0.f, 0.f}};   // rows (0, 1) and (2, 3) as register pairs
+    float mreg[MASKED ? TPC : 1][4];                                     // ReLU mask source of the sample in flight (data gradients)
+    vg_f2 bias_l[2];
+#pragma unroll
+    for (int r = 0; r < 2; ++r) { bias_l[r].x = bias ? bias[co_l + 2 * r] : 0.f; bias_l[r].y = bias ? bias[co_l + 2 * r + 1] : 0.f; }
     int nact = 0;                                                        // tiles this wave owns (wave-uniform)
 #pragma unroll
     for (int i = 0; i < TPC; ++i) nact += (i * MM_W + wave < ntiles) ? 1 : 0;
+    // (a tile the wave does not own holds no position of the block: pv is false for every lane, so its vbits bits are clear already)
 
     // stores a wave issues for class q (4 per tile with a lane that writes): what a counted vmcnt lets fly past the next input wait
     int nst[NQ];
@@ -208,58 +212,97 @@ conv_mm_k(const float* __restrict__ x, const float* __restrict__ a_img, const in
         nst[q] = c4;
     }
 
-    auto zero_acc = [&]() __attribute__((always_inline)) {
-#pragma unroll
-        for (int i = 0; i < TPC; ++i) { acc[i].v[0] = 0.f; acc[i].v[1] = 0.f; acc[i].v[2] = 0.f; acc[i].v[3] = 0.f; }
-    };
     // fetch the mask source of sample n's outputs (class 0) into registers; consumed by store_class
     auto load_mask = [&](int n) __attribute__((always_inline)) {
         const char* mn = reinterpret_cast<const char*>(mask_src + (size_t)n * CO * ovol);
 #pragma unroll
         for (int i = 0; i < TPC; ++i) {
             const bool okt = i < nact && ((vbits >> i) & 1u);
-            const unsigned off = okt ? 4u * (unsigned)(ob[i] + d.od0[0] * OHW + d.oh0[0] * d.OW + d.ow0[0]) : 0u;
+            const unsigned off = okt ? ob[i] + 4u * (unsigned)(d.od0[0] * OHW + d.oh0[0] * d.OW + d.ow0[0]) : 0u;
 #pragma unroll
             for (int r = 0; r < 4; ++r)
                 mreg[i][r] = okt ? *reinterpret_cast<const float*>(mn + (size_t)r * ovol * 4 + off) : 0.f;
         }
     };
-    // store class q of sample n from the accumulators: lane owns position jl of each tile, rows 4*kk .. 4*kk+3
-    auto store_class = [&](int n, int q) __attribute__((always_inline)) {
-        char* yn = reinterpret_cast<char*>(y + (size_t)n * CO * ovol);
-        const char* mn = reinterpret_cast<const char*>(mask_src + (size_t)n * CO * ovol);
-        const int cq = d.od0[q] * OHW + d.oh0[q] * d.OW + d.ow0[q];       // wave-uniform
+    // Store class q of sample n from the accumulators: lane owns position jl of each tile, rows 4*kk .. 4*kk+3.  What a launch fixes --
+    // rectified storage, statistics or not, statistics of max(v, 0) or of v -- are compile-time properties of the body (store_class
+    // picks the instance with ONE wave-uniform branch per class): per element the arithmetic is bias add, max, sum, sum of squares, in
+    // register pairs where the hardware has a packed form, and no select but the ReLU mask of a data gradient.  Addresses: a scalar
+    // base per row (sample, class offset and row are wave-uniform) + the tile's 32-bit lane offset.  The accumulators are left zero.
+    auto store_class_t = [&](int n, int q, auto relu_c, auto stats_c, auto srelu_c) __attribute__((always_inline)) {
+        constexpr bool RELU = !MASKED && decltype(relu_c)::value;        // rectified storage (a forward hand-off; masked stores ignore it)
+        constexpr bool STATS = decltype(stats_c)::value, SRELU = decltype(srelu_c)::value;
+        const long long cq4 = 4ll * (d.od0[q] * OHW + d.oh0[q] * d.OW + d.ow0[q]);
+        const size_t ovol4 = ovol * 4;
+        char* yq = reinterpret_cast<char*>(y + (size_t)n * CO * ovol) + cq4;
+        const char* mq = reinterpret_cast<const char*>(mask_src + (size_t)n * CO * ovol) + cq4;
+        float* yr[4]; const float* mr[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) { yr[r] = reinterpret_cast<float*>(yq + r * ovol4); mr[r] = reinterpret_cast<const float*>(mq + r * ovol4); }
+        // (touched: the per-tile lane predicates and the zero-extended offsets are formed here, at their use, not kept as scalar /
+        // vector register pairs across the matrix phase)
+        vg_touch(vbits);
 #pragma unroll
         for (int i = 0; i < TPC; ++i) {
-            if (i >= nact || !((vbits >> (q * TPC + i)) & 1u)) continue;
-            const unsigned off = 4u * (unsigned)(ob[i] + cq);             // bytes inside the sample: uniform base + 32-bit lane offset
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                float v = acc[i].v[r] + bias_l[r];
+            if ((vbits >> (q * TPC + i)) & 1u) {                         // (clear in every lane for a tile past the wave's last one)
+                vg_touch(ob[i]);
+                const unsigned off = ob[i];
+                float mk[4];
                 if constexpr (MASKED) {
-                    if constexpr (NQ == 1) v = (mreg[i][r] > 0.f) ? v : 0.f;                       // fetched before the matrix phase
-                    else v = (*reinterpret_cast<const float*>(mn + (size_t)r * ovol * 4 + off) > 0.f) ? v : 0.f;
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        if constexpr (NQ == 1) mk[r] = mreg[i][r];       // fetched before the matrix phase
+                        else mk[r] = vg_load_sbase(mr[r], off);
+                    }
                 }
-                const float vraw = v, vr = vg_max(v, 0.f);
-                if constexpr (!MASKED) { if (d.relu_out) v = vr; }       // rectified storage (a forward hand-off; masked stores ignore it)
+#pragma unroll
+                for (int r = 0; r < 4; r += 2) {
+                    const vg_f2 a2 = {acc[i].v[r], acc[i].v[r + 1]};
+                    vg_f2 v = vg_pk_add(a2, bias_l[r >> 1]);
+                    if constexpr (MASKED) { v.x = (mk[r] > 0.f) ? v.x : 0.f; v.y = (mk[r + 1] > 0.f) ? v.y : 0.f; }
+                    vg_f2 vr = v;
+                    if constexpr (RELU || (STATS && SRELU)) { vr.x = vg_max(v.x, 0.f); vr.y = vg_max(v.y, 0.f); }
+                    const vg_f2 vs = RELU ? vr : v;
+                    const float ve[2] = {vs.x, vs.y};
+#pragma unroll
+                    for (int e = 0; e < 2; ++e) {
 #if defined(VG_ABLATE_STORE) && VG_ABLATE_STORE == 1
-                if (v == 1.2345e-30f) *reinterpret_cast<float*>(yn + (size_t)r * ovol * 4 + off) = v;        // diagnostic: (almost) no store
+                        if (ve[e] == 1.2345e-30f) vg_store_sbase(yr[r + e], off, ve[e]);                            // diagnostic: (almost) no store
 #elif defined(VG_ABLATE_STORE) && VG_ABLATE_STORE == 2
-                *reinterpret_cast<float*>(yn + (size_t)r * ovol * 4 + (((off >> 8) << 8) + 4u * lane)) = v;    // diagnostic: one aligned 256-byte run per instruction
+                        *reinterpret_cast<float*>(reinterpret_cast<char*>(yr[r + e]) - cq4 + ((((off + (unsigned)cq4) >> 8) << 8) + 4u * lane)) = ve[e];   // diagnostic: one aligned 256-byte run per instruction
 #elif defined(VG_ABLATE_STORE) && VG_ABLATE_STORE == 4
-                if (r == 0 || v == 1.2345e-30f) *reinterpret_cast<float*>(yn + (size_t)r * ovol * 4 + off) = v;            // diagnostic: a quarter of the stores
+                        if (r + e == 0 || ve[e] == 1.2345e-30f) vg_store_sbase(yr[r + e], off, ve[e]);              // diagnostic: a quarter of the stores
 #elif defined(VG_ABLATE_STORE) && VG_ABLATE_STORE == 5
-                *reinterpret_cast<float*>(yn + off) = v;                                                         // diagnostic: all four stores to the first one's address
+                        vg_store_sbase(yr[0], off, ve[e]);                                                         // diagnostic: all four stores to the first one's address
 #elif defined(VG_ABLATE_STORE) && VG_ABLATE_STORE == 3
-                __builtin_nontemporal_store(v, reinterpret_cast<float*>(yn + (size_t)r * ovol * 4 + off));          // diagnostic: nt stores
+                        __builtin_nontemporal_store(ve[e], reinterpret_cast<float*>(reinterpret_cast<char*>(yr[r + e]) + off));   // diagnostic: nt stores
 #else
-                *reinterpret_cast<float*>(yn + (size_t)r * ovol * 4 + off) = v;
+                        vg_store_sbase(yr[r + e], off, ve[e]);
 #endif
-                if (stats_part) {
-                    const float h = stats_relu ? vr : vraw;                 // the same partials whether or not vr is also what is stored
-                    st_s[r] += h; st_q[r] = fmaf(h, h, st_q[r]);
+                    }
+                    if constexpr (STATS) {
+                        const vg_f2 h = SRELU ? vr : v;                    // the same partials whether or not vr is also what is stored
+                        st_s[r >> 1] = vg_pk_add(st_s[r >> 1], h); st_q[r >> 1] = vg_pk_fma(h, h, st_q[r >> 1]);
+                    }
                 }
             }
+            acc[i].v[0] = 0.f; acc[i].v[1] = 0.f; acc[i].v[2] = 0.f; acc[i].v[3] = 0.f;
+        }
+    };
+    const int emode = (stats_part ? (stats_relu ? 4 : 2) : 0) + ((!MASKED && d.relu_out) ? 1 : 0);   // wave-uniform, constant for the launch
+    auto store_class = [&](int n, int q) __attribute__((always_inline)) {
+        using T = std::bool_constant<true>; using F = std::bool_constant<false>;
+        if constexpr (MASKED) {
+            if (emode == 0) store_class_t(n, q, F{}, F{}, F{});
+            else if (emode == 2) store_class_t(n, q, F{}, T{}, F{});
+            else store_class_t(n, q, F{}, T{}, T{});
+        } else {
+            if (emode == 5) store_class_t(n, q, T{}, T{}, T{});
+            else if (emode == 2) store_class_t(n, q, F{}, T{}, F{});
+            else if (emode == 0) store_class_t(n, q, F{}, F{}, F{});
+            else if (emode == 1) store_class_t(n, q, T{}, F{}, F{});
+            else if (emode == 4) store_class_t(n, q, F{}, T{}, T{});
+            else store_class_t(n, q, T{}, T{}, F{});
         }
     };
     auto flush_stats = [&](int n) __attribute__((always_inline)) {
@@ -270,7 +313,7 @@ conv_mm_k(const float* __restrict__ x, const float* __restrict__ a_img, const in
         const size_t chunkid = ((size_t)(n % stats_pg) * p.bps + b) * MM_W + wave;
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-            float sa = st_s[r], sb = st_q[r];
+            float sa = (r & 1) ? st_s[r >> 1].y : st_s[r >> 1].x, sb = (r & 1) ? st_q[r >> 1].y : st_q[r >> 1].x;
 #pragma unroll
             for (int off = 8; off > 0; off >>= 1) { sa += __shfl_xor(sa, off); sb += __shfl_xor(sb, off); }
             if (CO == 8) { sa += __shfl_xor(sa, 32); sb += __shfl_xor(sb, 32); }   // the two replicas of a channel
@@ -278,8 +321,9 @@ conv_mm_k(const float* __restrict__ x, const float* __restrict__ a_img, const in
                 double* dst = stats_part + (((size_t)g * CO + co_l + r) * chunks + chunkid) * 2;
                 dst[0] = (double)sa; dst[1] = (double)sb;
             }
-            st_s[r] = 0.f; st_q[r] = 0.f;
         }
+#pragma unroll
+        for (int r = 0; r < 2; ++r) { st_s[r].x = 0.f; st_s[r].y = 0.f; st_q[r].x = 0.f; st_q[r].y = 0.f; }
     };
 
     // Input of unit u (sample, channel chunk): per channel the staged rows of every staged plane -- one contiguous span per plane, or one
@@ -430,7 +474,6 @@ conv_mm_k(const float* __restrict__ x, const float* __restrict__ a_img, const in
         const int g_now = stats_part ? n / stats_pg : 0;
         if (stats_part && chunk == 0 && g_run >= 0 && g_now != g_run) flush_stats(n_run);   // the run of g_run's samples has ended
         if constexpr (NQ == 1) {
-            if (chunk == 0) zero_acc();
             if (nact > 0) mm_dispatch<TPC>(nact, [&](auto ntc) __attribute__((always_inline)) { class_work(mm_int<0>{}, ntc); });
             VG_STAMP_ADD(4);
             pend = 0;
@@ -445,7 +488,6 @@ conv_mm_k(const float* __restrict__ x, const float* __restrict__ a_img, const in
             // all channels are resident (the host plans one chunk per sample for multi-class layers)
             mm_static_for<NQ>([&](auto qc) __attribute__((always_inline)) {
                 constexpr int q = decltype(qc)::value;
-                zero_acc();
                 VG_STAMP_ADD(5);
                 if (nact > 0) mm_dispatch<TPC>(nact, [&](auto ntc) __attribute__((always_inline)) { class_work(qc, ntc); });
                 VG_STAMP_ADD(4);
