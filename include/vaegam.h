@@ -400,6 +400,26 @@ typedef struct vg_fc_job {
 } vg_fc_job;
 int vg_fc_gemm_jobs(const vg_fc_job* jobs, int32_t njobs, void* stream);
 
+/* What vg_fc_gemm_jobs (vg_fc_gemm: njobs = 1) would launch for these jobs: nothing is launched and no memory is touched, the
+ * pointers are read for their 16-byte alignment only.  The record comes from the function that builds the launch for
+ * vg_fc_gemm_jobs.  out[0 .. VG_FC_PLAN_LEN):
+ *    0 tile  1 grid  2 reduce_blocks  3 njobs                       tile edge (32: fc_gemm_k<1>, 64: fc_gemm_k<2>; one for all jobs),
+ *                                                                   blocks of the product launch, blocks of the split-K reduction
+ *                                                                   (0: no second launch), jobs
+ *   per job j, from out[4 + 8*j]:
+ *    0 a_vec  1 b_vec                                               load form of A / B (0 dwords, 1 16 bytes along k, 2 16 bytes
+ *                                                                   along m / n): the body fc_body<W, a_vec, b_vec> the job runs
+ *    2 big                                                          the job's own vote for 64 x 64 (>= 768 tiles of 32 x 32); the launch
+ *                                                                   runs 64 x 64 only if every job votes for it
+ *    3 kchunk                                                       reduction indices per split piece (a multiple of 64)
+ *    4 gx  5 gy                                                     tiles along m and n (n counts the ones column) at the launch's tile
+ *    6 first  7 blocks                                              the job's first block and block count (gx * gy * (ksplit or batch))
+ *   the records of jobs >= njobs are 0.
+ * n_out < VG_FC_PLAN_LEN (or out NULL) returns VG_ERR_ARG; every job list the launcher refuses returns the launcher's status and leaves
+ * the launcher's text in vg_last_error(). */
+#define VG_FC_PLAN_LEN 36
+int vg_fc_plan(const vg_fc_job* jobs, int32_t njobs, int32_t* out, int32_t n_out);
+
 /* Re-pack every conv / transposed-conv weight of the model into the [ci][tap][co] images vg_corr3d / vg_tconv3d_s2 read,
  * in one launch from the flat fp32 parameter buffer.  segs: device array [nseg][8] of int64
  * {src offset, dst offset, d0, d1, taps, mode, element count, 0} sorted by dst offset; w is [d0][d1][taps];

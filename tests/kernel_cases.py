@@ -2,6 +2,8 @@
 maths -- fp32 for the layer and chain cases, float64 where a case's docstring says so (the conv_mm, weight-gradient,
 FC and gain case matrices; the batch-norm kernels have theirs in bn_cases.py).  Run on CPU tensors through the host build of the kernels
 (tests/emu, index-arithmetic check) and on the GPU through libvaegam_hip.so (-m gpu)."""
+import types
+
 import numpy as np
 import torch
 import torch.nn.functional as F
@@ -1135,6 +1137,49 @@ def wgrad_production_plans():
                     out.append((img, B, C, spec.name, ops.wgrad_plan(spec, *_wgrad_shapes(spec, isz, N), True, B)))
             spec, isz = geo.dec[-1], geo.dec_sizes()[-2]
             out.append((img, B, C, spec.name + '/grouped', ops.wgrad_plan(spec, *_wgrad_shapes(spec, isz, B * (C + 1)), True, B, grouped=True)))
+    return out
+
+
+def fc_production_plans(L=32):
+    """-> [(what, plan, [(ksplit, batch) per job])] for every fully connected launch of a train step of the three networks at the bench
+    sample counts: LinearAct and HeadsAct are driven forward and backward on CPU tensors of the production shapes (parameters with
+    16-byte aligned .grad views, as the optimiser lays them out) with ops.fc_launch replaced by a recorder that asks ops.fc_plan:
+    nothing is launched and no tensor is read, only shapes and pointers flow."""
+    from vae_gam_amd.schema import net_geometry
+    out, tag = [], ['']
+
+    def record(ref, jobs):
+        what = ' + '.join('%dx%dx%d' % (j[0].d.M, j[0].d.N, j[0].d.K) for j in jobs)
+        out.append(('%s %s' % (tag[0], what), ops.fc_plan(jobs), [(int(j[0].d.ksplit), int(j[0].d.batch)) for j in jobs]))
+
+    def linear(fin, fout):
+        lay = types.SimpleNamespace(weight=torch.nn.Parameter(torch.empty(fout, fin)), bias=torch.nn.Parameter(torch.empty(fout)))
+        lay.weight.grad = torch.empty_like(lay.weight); lay.bias.grad = torch.empty_like(lay.bias)
+        return lay
+    H = 50
+    saved = ops.fc_launch
+    ops.fc_launch = record
+    try:
+        for img, cfgs in WGRAD_NETS:
+            geo = net_geometry(img)
+            for B, C in cfgs:
+                name = '%s B%d C%d ' % ('x'.join(map(str, img)), B, C)
+                fc1, fc2 = linear(geo.enc_flat, 200), linear(200, 100)
+                heads = [torch.empty(s) for s in ((3 * H, 100), (3 * H,), (3, L, H), (3, 1, L))] * 2
+                tag[0] = name + 'encoder'
+                x = torch.empty(B, geo.enc_flat, requires_grad=True)
+                h = ops.linear_act(fc2, ops.linear_act(fc1, x, True, relu_in=True), True)
+                mwa = ops.HeadsAct.apply(h, *heads)
+                mwa.backward(torch.empty_like(mwa))
+                tag[0] = name + 'decoder'
+                z = torch.empty(B * (C + 1), L + C + 1, requires_grad=True)
+                lays = [linear(L + C + 1, 50), linear(50, 100), linear(100, 200), linear(200, geo.dec_flat)]
+                h = z
+                for i, lay in enumerate(lays):
+                    h = ops.linear_act(lay, h, i < 3)
+                h.backward(torch.empty_like(h))
+    finally:
+        ops.fc_launch = saved
     return out
 
 

@@ -3,7 +3,9 @@ the GPU box: the shrunk per-layer cases of tests/kernel_cases.py plus every laye
 reference's real 41x49x35 geometry.  The real geometry is not the production launch: at the 2 or 4 samples
 these cases use, every 3x3x3 layer falls under the direct engine's `small` switch and runs the 4-channel
 instances, not the 8-wide plane-staged / transposed ones a training batch takes.  Those are pinned, class by
-class and against float64, by tests/conv_direct_cases.py (test_conv_direct_gpu.py)."""
+class and against float64, by tests/conv_direct_cases.py (test_conv_direct_gpu.py).  Likewise the fully connected
+cases here keep the network sizes; the bodies fc_body<W, a_vec, b_vec>, tile sizes and job mixes of vg_fc.hip are
+pinned, plan by plan and against float64, in tests/fc_cases.py (test_fc_gpu.py)."""
 import numpy as np
 import pytest
 import torch

@@ -113,6 +113,7 @@ _PROTOS = {
     'vg_fc_ws_bytes': (i64, [ctypes.POINTER(FcDesc)]),
     'vg_fc_gemm': (ctypes.c_int, [ctypes.POINTER(FcDesc), vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     'vg_fc_gemm_jobs': (ctypes.c_int, [ctypes.POINTER(FcJob), i32, vp]),
+    'vg_fc_plan': (ctypes.c_int, [ctypes.POINTER(FcJob), i32, ctypes.POINTER(i32), i32]),
     'vg_gp_gain_ws_bytes': (i64, [i32, i32, i32]),
     'vg_gp_gain_fwd': (ctypes.c_int, [ctypes.POINTER(GainDesc), vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     'vg_gp_gain_bwd': (ctypes.c_int, [ctypes.POINTER(GainDesc), vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp]),
@@ -132,6 +133,9 @@ CONV_PLAN_FIELDS = ('family', 'COT', 'KD', 'KH', 'KW', 'S', 'TDt', 'THt', 'TW', 
                     'tilesD', 'threads', 'grid_x', 'grid_y', 'grid_z', 'LD', 'CCH', 'chunks', 'nbuf', 'OHB', 'nhb', 'LH', 'lplane', 'ch_floats',
                     'lds_bytes', 'JD', 'JH', 'JW', 'stats_chunks')                                           # VG_CONV_PLAN_LEN, in order
 CONV_FAMILIES = ('direct', 'plane', 'tconv')                                                                # values of field 0
+FC_PLAN_LEN = 36               # VG_FC_PLAN_LEN: 4 head values, then 8 per job (FC_PLAN_JOB_FIELDS) for up to 4 jobs
+FC_PLAN_HEAD_FIELDS = ('tile', 'grid', 'reduce_blocks', 'njobs')
+FC_PLAN_JOB_FIELDS = ('a_vec', 'b_vec', 'big', 'kchunk', 'gx', 'gy', 'first', 'blocks')
 GUARD_STATE_LEN = 8            # VG_GUARD_STATE_LEN: [total_norm, scale, apply, seen, skipped, clipped, norm_sum, norm_max]
 EXPORTS = tuple(_PROTOS)
 

@@ -379,9 +379,15 @@ extern "C" int64_t vg_fc_ws_bytes(const vg_fc_desc* d) {
     return (int64_t)d->ksplit * d->M * (d->N + ((d->flags & VG_FC_B_ONES) ? 1 : 0)) * (int64_t)sizeof(float);
 }
 
-extern "C" int vg_fc_gemm_jobs(const vg_fc_job* jobs, int32_t njobs, void* stream) {
+namespace {
+
+// Everything a launch is: the argument block of both kernels, the tile, the grid of the product launch and of the reduction (0: none).
+// vg_fc_gemm_jobs launches it, vg_fc_plan reports it.
+struct FcLaunch { FcJobs js; bool big; int grid; int reduce_blocks; };
+
+int fc_plan_launch(const vg_fc_job* jobs, int32_t njobs, FcLaunch* L) {
     if (!jobs || njobs < 1 || njobs > FC_MAXJOBS) { vg_set_error("vg_fc_gemm_jobs: 1..%d jobs", FC_MAXJOBS); return VG_ERR_ARG; }
-    FcJobs js; js.n = njobs; js.first[0] = 0;
+    FcJobs& js = L->js; js.n = njobs; js.first[0] = 0;
     bool any_split = false; size_t red = 0;
     bool big = true;
     for (int j = 0; j < njobs; ++j) {
@@ -398,14 +404,40 @@ extern "C" int vg_fc_gemm_jobs(const vg_fc_job* jobs, int32_t njobs, void* strea
         js.first[j + 1] = js.first[j] + (int)nb;
         if (d.ksplit > 1) { any_split = true; const size_t t = (size_t)d.M * (d.N + 1); if (t > red) red = t; }
     }
+    L->big = big; L->grid = js.first[njobs]; L->reduce_blocks = 0;
+    if (any_split) { int nb = (int)((red + 255) / 256); if (nb > 1024) nb = 1024; L->reduce_blocks = nb; }
+    return VG_OK;
+}
+
+}  // namespace
+
+extern "C" int vg_fc_gemm_jobs(const vg_fc_job* jobs, int32_t njobs, void* stream) {
+    FcLaunch L;
+    const int rc = fc_plan_launch(jobs, njobs, &L);
+    if (rc != VG_OK) return rc;
     hipStream_t s = (hipStream_t)stream;
-    if (big) vg_launch(fc_gemm_k<2>, dim3(js.first[njobs]), dim3(256), 0, s, js);
-    else vg_launch(fc_gemm_k<1>, dim3(js.first[njobs]), dim3(256), 0, s, js);
+    if (L.big) vg_launch(fc_gemm_k<2>, dim3(L.grid), dim3(256), 0, s, L.js);
+    else vg_launch(fc_gemm_k<1>, dim3(L.grid), dim3(256), 0, s, L.js);
     const int r2 = vg_check_launch("fc_gemm");
-    if (r2 != VG_OK || !any_split) return r2;
-    int nb = (int)((red + 255) / 256); if (nb > 1024) nb = 1024;
-    vg_launch(fc_reduce_k, dim3(nb), dim3(256), 0, s, js);
+    if (r2 != VG_OK || !L.reduce_blocks) return r2;
+    vg_launch(fc_reduce_k, dim3(L.reduce_blocks), dim3(256), 0, s, L.js);
     return vg_check_launch("fc_reduce");
+}
+
+extern "C" int vg_fc_plan(const vg_fc_job* jobs, int32_t njobs, int32_t* out, int32_t n_out) {
+    if (!out || n_out < VG_FC_PLAN_LEN) { vg_set_error("vg_fc_plan: out must hold %d values", VG_FC_PLAN_LEN); return VG_ERR_ARG; }
+    FcLaunch L;
+    const int rc = fc_plan_launch(jobs, njobs, &L);
+    if (rc != VG_OK) return rc;
+    for (int i = 0; i < VG_FC_PLAN_LEN; ++i) out[i] = 0;
+    out[0] = L.big ? 64 : 32; out[1] = L.grid; out[2] = L.reduce_blocks; out[3] = njobs;
+    for (int j = 0; j < njobs; ++j) {
+        const FcArgs& p = L.js.job[j];
+        int32_t* o = out + 4 + 8 * j;
+        o[0] = p.a_vec; o[1] = p.b_vec; o[2] = p.big; o[3] = p.kchunk; o[4] = p.gx; o[5] = p.gy;
+        o[6] = L.js.first[j]; o[7] = L.js.first[j + 1] - L.js.first[j];
+    }
+    return VG_OK;
 }
 
 extern "C" int vg_fc_gemm(const vg_fc_desc* d, const float* A, const float* amask, const float* B, const float* bias, const float* cmask,

@@ -1008,16 +1008,16 @@ def _fc_split(M, N, K):
 
 
 def fc_job(A, B, C, M, N, K, a_strides, b_strides, c_strides, flags=0, batch=1, bias=None, bias_sb=0, amask=None, cmask=None,
-           cx=None, cx_sb=0, ksplit=None):
+           cx=None, cx_sb=0, ksplit=None, ws=None):
     """One product for vg_fc_gemm_jobs: C[z][m][n] (+)= epilogue(sum_k A[z](m,k) B[z](k,n)); a_strides = (sm, sk, sb),
-    b_strides = (sk, sn, sb), c_strides = (sm, sb), all in elements (include/vaegam.h).  Returns (job struct, tensors to keep alive)."""
+    b_strides = (sk, sn, sb), c_strides = (sm, sb), all in elements (include/vaegam.h).  ws: the caller's own split-K workspace
+    (at least vg_fc_ws_bytes; one is allocated when it is None).  Returns (job struct, tensors to keep alive)."""
     lib = _lib.get_lib()
     if ksplit is None:
         ksplit = _fc_split(M, N + (1 if flags & _lib.FC_B_ONES else 0), K) if batch == 1 else 1
     d = _lib.FcDesc(M, N, K, batch, a_strides[0], a_strides[1], a_strides[2], b_strides[0], b_strides[1], b_strides[2],
                     c_strides[0], c_strides[1], bias_sb, cx_sb, ksplit, flags)
-    ws = None
-    if ksplit > 1:
+    if ksplit > 1 and ws is None:
         ws = torch.empty(lib.size('vg_fc_ws_bytes', ctypes.byref(d)) // 4, dtype=torch.float32, device=C.device)
     ptr = lambda t: None if t is None else t.data_ptr()
     return _lib.FcJob(d, ptr(A), ptr(amask), ptr(B), ptr(bias), ptr(cmask), ptr(C), ptr(cx), ptr(ws)), (A, B, C, bias, amask, cmask, cx, ws)
@@ -1027,6 +1027,17 @@ def fc_launch(ref, jobs):
     """vg_fc_gemm_jobs: the products of `jobs` (fc_job results, <= 4) in one launch on ref's stream."""
     arr = (_lib.FcJob * len(jobs))(*[j[0] for j in jobs])
     _call(ref, 'vg_fc_gemm_jobs', arr, len(jobs))
+
+
+def fc_plan(jobs):
+    """What fc_launch(jobs) would launch, from the launcher's own planner (vg_fc_plan): nothing is launched, no memory is touched.
+    -> dict(tile, grid, reduce_blocks, njobs, jobs=[dict(a_vec, b_vec, big, kchunk, gx, gy, first, blocks), ...])."""
+    arr = (_lib.FcJob * max(len(jobs), 1))(*[j[0] for j in jobs])
+    rec = (ctypes.c_int32 * _lib.FC_PLAN_LEN)()
+    _lib.get_lib().call('vg_fc_plan', arr, len(jobs), rec, len(rec))
+    plan = dict(zip(_lib.FC_PLAN_HEAD_FIELDS, (int(v) for v in rec[:4])))
+    plan['jobs'] = [dict(zip(_lib.FC_PLAN_JOB_FIELDS, (int(v) for v in rec[4 + 8 * j:12 + 8 * j]))) for j in range(plan['njobs'])]
+    return plan
 
 
 def fc_gemm(A, B, C, *args, **kw):
