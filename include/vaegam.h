@@ -297,6 +297,25 @@ int vg_gam_elbo_bwd_masked(const float* logits, const float* gain, const float* 
                            int32_t C, int32_t B, const int32_t* nat, const int32_t* grid, void* ws,
                            float* d_logits, float* d_gain, double* d_eps, float* d_total, int32_t total_accumulate, void* stream);
 
+/* Voxel-wise statistics of the maps and of the fit (an extension; the reference re-reads every per-volume NIfTI for its averages and has
+ * no second moments): per-subject running sums over the volumes of a minibatch, straight from the logits, in ONE launch.
+ *   logits [C+1][B][V_G], gain [C][B], x [B][V_N]: as vg_gam_elbo_fwd_masked;  subj int32 [B]: the subject slot of each volume;
+ *   mask uint8 [V_N] or NULL (every native voxel counts);  nat / grid: host arrays of three, as the _masked pair (nat == grid runs the
+ *   instances without the index decode);  acc double [S][K][V_N], read and written, K = vg_gam_stats_slots(C) = 3C + 8.
+ * Per volume and voxel, gam_fwd's maps by its own fp32 expressions: base = sigmoid(logit_0), cons_i = gain_i * sigmoid(logit_i),
+ * rec = base + sum_i cons_i (in i order), r = x - rec.  Slots of a subject (sums over its volumes; squares and sums formed in fp64 from
+ * the fp32 values):
+ *   0 .. C+1        sum of base, cons_1..C, rec          C+2 .. 2C+3     sum of their squares
+ *   2C+4  sum x     2C+5  sum x^2     2C+6  sum r     2C+7  sum r^2      2C+8 .. 3C+7    sum (r + cons_i)^2
+ * One thread owns a voxel of one subject for the whole launch: it folds that subject's volumes in ascending b into registers that
+ * start at 0 and then adds each partial to its entry of acc once.  No atomics: two runs give the same bits.  The slab of a subject with
+ * no volume in the batch, and every entry of a voxel outside the mask, keep their bits (the padding has no entry).  A subj[b] outside
+ * [0, S) is skipped.  Refused: null pointers, C < 0, B <= 0, B > 65535, S <= 0, S > 65535, a nat that does not fit into a grid of less
+ * than 2^31 voxels (VG_ERR_ARG); C > 16 (VG_ERR_UNSUPPORTED; vg_gam_stats_slots: -1). */
+int32_t vg_gam_stats_slots(int32_t C);
+int vg_gam_stats_accumulate(const float* logits, const float* gain, const float* x, const int32_t* subj, const uint8_t* mask,
+                            int32_t C, int32_t B, int32_t S, const int32_t* nat, const int32_t* grid, double* acc, void* stream);
+
 /* Batch-norm parameter gradients from vg_bn_bwd_reduce's per-(group, channel) sums:
  *   dgamma[c] (+)= sum_g sums[g][c][1],  dbeta[c] (+)= sum_g sums[g][c][0]   (accumulate != 0 adds into the .grad buffers;
  *   replaces autograd's sum + add launches after torch.nn.BatchNorm3d's backward, vae_reg_GP.py:195-201,216-222). */

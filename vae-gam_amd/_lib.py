@@ -105,6 +105,8 @@ _PROTOS = {
     'vg_gam_elbo_fwd_masked': (ctypes.c_int, [vp, vp, vp, vp, vp, vp, i32, i32, ctypes.POINTER(i32), ctypes.POINTER(i32), vp, vp, vp, vp, vp]),
     'vg_gam_elbo_bwd_masked': (ctypes.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, ctypes.POINTER(i32), ctypes.POINTER(i32), vp, vp, vp,
                                               vp, vp, i32, vp]),
+    'vg_gam_stats_slots': (i32, [i32]),
+    'vg_gam_stats_accumulate': (ctypes.c_int, [vp, vp, vp, vp, vp, i32, i32, i32, ctypes.POINTER(i32), ctypes.POINTER(i32), vp, vp]),
     'vg_pack_weights': (ctypes.c_int, [vp, vp, vp, i32, i64, vp]),
     'vg_cholesky_f64': (ctypes.c_int, [vp, vp, i32, i32, vp]),
     'vg_conv_mm_stats_chunks': (i64, [ctypes.POINTER(MmDesc), i32]),

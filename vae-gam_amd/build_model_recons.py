@@ -60,3 +60,42 @@ def mk_avg_maps(csv_file, model, save_dir, mk_motion_maps=False, loader=None):
         nifti.write_nifti1(os.path.join(avg_dir, '{}_avg.nii'.format(m)), grand.reshape(shape), ref0)
         out[m] = grand.reshape(shape)
     return out
+
+
+def _ref_or_none(ref_niis, i):
+    ok = i < len(ref_niis) and str(ref_niis[i]).endswith(('.nii', '.nii.gz')) and os.path.exists(str(ref_niis[i]))
+    return ref_niis[i] if ok else None
+
+
+def mk_stat_maps(csv_file, model, save_dir, loader, mk_motion_maps=False, at_mean=False):
+    """Voxel-wise statistics next to the averages (an extension; VAE.map_statistics): under
+    reconstructions/<ckpt>_stat_model_recons/, per subject `<map>_std.nii` (standard deviation of the map over the subject's volumes),
+    `r2.nii` (variance of the data the model explains) and `<covariate map>_partial_r2.nii`; at top level `<map>_t.nii` (one-sample t
+    over the subject means) and `r2_avg.nii` (mean of the subjects' r2).  Reference geometry and map selection as mk_avg_maps; one
+    pass over `loader`, nothing is read back from the per-volume files.  Returns the MapStatistics."""
+    subjs, ref_niis = _subjects(csv_file)
+    stats = model.map_statistics(loader, num_subjects=len(subjs), at_mean=at_mean)
+    ckpt_num = str(model.epoch).zfill(3)
+    stat_dir = os.path.join(save_dir, 'reconstructions', '{}_stat_model_recons'.format(ckpt_num))
+    os.makedirs(stat_dir, exist_ok=True)
+    keys = list(stats.keys)
+    maps = [m for m in MAPS_ALL if m in keys] + [k for k in keys if k not in MAPS_ALL]
+    if not mk_motion_maps:
+        maps = [m for m in maps if m in ('base', 'task', 'full_rec', 'sex')]
+    covs = [m for m in maps if m in keys[1:-1]]
+    shape = tuple(model.img_shape)
+
+    def host(t):
+        return t.cpu().numpy().astype(np.float64)
+
+    per_subject = [('{}_std.nii'.format(m), host(stats.subject_std(m))) for m in maps] + [('r2.nii', host(stats.r2()))] + \
+                  [('{}_partial_r2.nii'.format(m), host(stats.partial_r2(m))) for m in covs]
+    for i, s in enumerate(subjs):
+        d = os.path.join(stat_dir, str(s)); os.makedirs(d, exist_ok=True)
+        for name, arr in per_subject:
+            nifti.write_nifti1(os.path.join(d, name), arr[i].reshape(shape), _ref_or_none(ref_niis, i))
+    ref0 = _ref_or_none(ref_niis, 0)
+    for m in maps:
+        nifti.write_nifti1(os.path.join(stat_dir, '{}_t.nii'.format(m)), host(stats.group_t(m)).reshape(shape), ref0)
+    nifti.write_nifti1(os.path.join(stat_dir, 'r2_avg.nii'), host(stats.group_r2()).reshape(shape), ref0)
+    return stats

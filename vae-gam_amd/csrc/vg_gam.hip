@@ -276,6 +276,153 @@ __global__ void gam_bwd_fold_eps_k(const float* __restrict__ part_dsig, const do
     d_eps[v] = (double)a * (-exp(-eps[v]));
 }
 
+// ---------------------------------------------------------------------------------- voxel-wise statistics of the maps and of the fit
+// The volumes of subject s inside a batch, in ascending order.  subj[] is scanned 64 volumes at a time: every lane of a wave tests one
+// entry and the ballot is a wave-uniform bit set, so walking the members costs scalar instructions only (one vector load per 64 volumes,
+// not one dependent scalar load per volume).  An entry outside [0, S) matches no block's s and is never a member.
+#ifdef VG_EMU
+static inline unsigned long long stats_members(const int32_t* subj, int b0, int B, int s) {
+    unsigned long long m = 0;
+    for (int k = 0; k < VG_WAVE && b0 + k < B; ++k) if (subj[b0 + k] == s) m |= 1ull << k;
+    return m;
+}
+#else
+__device__ __forceinline__ unsigned long long stats_members(const int32_t* subj, int b0, int B, int s) {
+    const int b = b0 + (int)(threadIdx.x % VG_WAVE);
+    return __builtin_amdgcn_ballot_w64(b < B && subj[b] == s);
+}
+#endif
+// No instruction: marks a wave-uniform value as redefined, in a scalar register.  The `i < C` tests of the unrolled covariate loops are
+// loop invariants; hoisted, each is kept as a 64-bit lane mask for the whole batch loop (2 * CMAX scalar registers: spills).  Computed
+// from a value redefined inside the loop they stay one s_cmp in front of their branch.
+#ifdef VG_EMU
+static inline int stats_here(int c) { return c; }
+#else
+__device__ __forceinline__ int stats_here(int c) { asm volatile("" : "+s"(c)); return c; }
+#endif
+struct StatsMembers {
+    const int32_t* subj;
+    int B, s, b0;
+    unsigned long long m;
+    __device__ __forceinline__ int next() {                            // -> the next member, or -1 (and -1 from then on)
+        while (!m) {
+            b0 += VG_WAVE;
+            if (b0 >= B) { b0 = B; return -1; }
+            m = stats_members(subj, b0, B, s);
+        }
+        const int k = __builtin_ctzll(m);
+        m &= m - 1;
+        return b0 + k;
+    }
+};
+
+// what one thread loads of one volume ahead of its arithmetic: its voxel's C+1 logits and data value
+template <int CMAX>
+struct StatsRaw { float lg[CMAX + 1], x; };
+
+// acc[s][k][vn] += the sums over subject s's volumes of this batch (slot table: include/vaegam.h).  grid (vblocks, S): a thread owns
+// voxel v of subject blockIdx.y for the whole launch, folds that subject's volumes in ascending b into fp64 registers that start at
+// 0 and adds each of them to its accumulator entry ONCE -- no atomics, the same bits on every run.  The map values are gam_fwd_k's, by
+// the same fp32 expressions; sums and squares are formed in fp64 from them.
+// Latency, not occupancy, is what has to be hidden (about one block per CU and subject at 41x49x35): the volumes go in groups of U
+// whose (C+2) * U loads per lane are issued together, and the loads of group g+1 are issued BEFORE the arithmetic of group g.
+// CMAX: compile-time bound of the covariate loops (fully unrolled: every register array is indexed by constants); EMB / MSK as in
+// gam_bwd_k.  A thread on a voxel that does not count (behind the end, padding, outside the mask) loads nothing and writes nothing;
+// a block whose subject has no volume in the batch writes nothing.
+template <int CMAX, int U, bool EMB, bool MSK>
+__global__ void __launch_bounds__(GT)
+gam_stats_k(const float* __restrict__ logits, const float* __restrict__ gain, const float* __restrict__ x, const int32_t* __restrict__ subj,
+            const uint8_t* __restrict__ mask, int C_, int B, long long V, double* __restrict__ acc, GamGrid e) {
+    const int s = blockIdx.y;
+    const long long v = (long long)blockIdx.x * GT + threadIdx.x;
+    const bool ok = v < V;
+    long long nc = ok ? v : 0;                                         // the voxel's index in the native tensors
+    bool nat = ok;                                                     // a voxel that counts
+    if (EMB) { nat = grid_to_native(e, ok ? v : 0, nc) && ok; if (!nat) nc = 0; }
+    if (MSK) nat = nat && mask[nc] != 0;
+    const long long Vn = EMB ? e.Vn : V;
+    const size_t BV = (size_t)B * V;
+    StatsMembers it{subj, B, s, -VG_WAVE, 0ull};
+    StatsRaw<CMAX> nxt[U];
+    int nb[U];
+    auto fetch = [&]() {
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            nb[u] = it.next();
+            const int b = nb[u], C = stats_here(C_);
+            nxt[u].x = 0.f;
+#pragma unroll
+            for (int i = 0; i <= CMAX; ++i) nxt[u].lg[i] = 0.f;
+            if (b >= 0 && nat) {
+                const float* lp = logits + ((size_t)b * V + v);          // a running pointer: one uniform stride, not CMAX offsets
+                nxt[u].x = x[(size_t)b * Vn + nc];
+                nxt[u].lg[0] = *lp;
+#pragma unroll
+                for (int i = 0; i < CMAX; ++i) if (i < C) { lp += BV; nxt[u].lg[i + 1] = *lp; }
+            }
+        }
+    };
+    double sm[CMAX + 1], sq[CMAX + 1], sp[CMAX];                       // base and cons_i: sums, sums of squares; sums of (r + cons_i)^2
+#pragma unroll
+    for (int i = 0; i <= CMAX; ++i) sm[i] = sq[i] = 0.0;
+#pragma unroll
+    for (int i = 0; i < CMAX; ++i) sp[i] = 0.0;
+    double s_rec = 0.0, q_rec = 0.0, s_x = 0.0, q_x = 0.0, s_r = 0.0, q_r = 0.0;
+    int n = 0;                                                         // volumes folded (block-uniform)
+    fetch();
+    while (nb[0] >= 0) {
+        StatsRaw<CMAX> cur[U];
+        int cb[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) { cur[u] = nxt[u]; cb[u] = nb[u]; }
+        fetch();
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            if (cb[u] < 0) continue;                                   // wave-uniform
+            ++n;
+            const int C = stats_here(C_);
+            float cons[CMAX];
+            const float base = sigmoidf_(cur[u].lg[0]);
+            float xrec = base;
+            const float* gp = gain + cb[u];                            // (the gains: scalar loads)
+#pragma unroll
+            for (int i = 0; i < CMAX; ++i) {
+                cons[i] = 0.f;
+                if (i < C) { cons[i] = *gp * sigmoidf_(cur[u].lg[i + 1]); xrec += cons[i]; gp += B; }
+            }
+            const float r = cur[u].x - xrec;
+            const double bd = base, xd = cur[u].x, rd = r, recd = xrec;
+            sm[0] += bd; sq[0] += bd * bd;
+            s_rec += recd; q_rec += recd * recd;
+            s_x += xd; q_x += xd * xd;
+            s_r += rd; q_r += rd * rd;
+#pragma unroll
+            for (int i = 0; i < CMAX; ++i) {
+                const double cd = cons[i], t = rd + cd;                // (beyond C: cons = 0, sums that are never written)
+                sm[i + 1] += cd; sq[i + 1] += cd * cd; sp[i] += t * t;
+            }
+        }
+    }
+    if (!nat || n == 0) return;
+    const int C = C_;
+    const size_t Vs = (size_t)Vn;
+    double* a = acc + (size_t)s * (size_t)(3 * C + 8) * Vs + (size_t)nc;      // walks the subject's slots in order
+    *a += sm[0]; a += Vs;
+#pragma unroll
+    for (int i = 0; i < CMAX; ++i) if (i < C) { *a += sm[i + 1]; a += Vs; }
+    *a += s_rec; a += Vs;
+    *a += sq[0]; a += Vs;
+#pragma unroll
+    for (int i = 0; i < CMAX; ++i) if (i < C) { *a += sq[i + 1]; a += Vs; }
+    *a += q_rec; a += Vs;
+    *a += s_x; a += Vs;
+    *a += q_x; a += Vs;
+    *a += s_r; a += Vs;
+    *a += q_r; a += Vs;
+#pragma unroll
+    for (int i = 0; i < CMAX; ++i) if (i < C) { *a += sp[i]; a += Vs; }
+}
+
 int fwd_chunks(long long V) { return (int)((V + (long long)GT * GV - 1) / ((long long)GT * GV)); }
 int bwd_vblocks(long long V) { return (int)((V + GT - 1) / GT); }
 int bwd_gain_parts(long long V) { return bwd_vblocks(V) * (GT / VG_WAVE); }
@@ -556,6 +703,32 @@ extern "C" int vg_gam_elbo_bwd_masked(const float* logits, const float* gain, co
     if (!mask) { vg_set_error("vg_gam_elbo_bwd_masked: no mask"); return VG_ERR_ARG; }
     return gam_bwd(logits, gain, x, eps, glm, dist, g_slp, g_dist, C, B, V, e.Vn == V ? nullptr : &e, mask, ws, d_logits, d_gain, d_eps, d_total,
                    total_accumulate, stream);
+}
+
+extern "C" int32_t vg_gam_stats_slots(int32_t C) { return (C < 0 || C > GMAXC) ? -1 : 3 * C + 8; }
+
+// nat == grid: the instances without the index decode; mask may be null
+extern "C" int vg_gam_stats_accumulate(const float* logits, const float* gain, const float* x, const int32_t* subj, const uint8_t* mask,
+                                       int32_t C, int32_t B, int32_t S, const int32_t* nat, const int32_t* grid, double* acc, void* stream) {
+    if (!logits || !x || !subj || !acc || (C > 0 && !gain) || C < 0 || B <= 0 || B > 65535 || S <= 0 || S > 65535) {
+        vg_set_error("vg_gam_stats_accumulate: bad arguments C=%d B=%d S=%d", C, B, S); return VG_ERR_ARG;
+    }
+    if (C > GMAXC) { vg_set_error("vg_gam_stats_accumulate: more than 16 covariates"); return VG_ERR_UNSUPPORTED; }
+    GamGrid e;
+    const long long V = make_grid(nat, grid, e);
+    if (V < 0) { vg_set_error("vg_gam_stats_accumulate: the native grid must fit into a grid of less than 2^31 voxels"); return VG_ERR_ARG; }
+    const bool emb = e.Vn != V;
+    hipStream_t s = (hipStream_t)stream;
+#define VG_GAM_STATS(CMAX, U, EMB, MSK)                                                                                                \
+    vg_launch(gam_stats_k<CMAX, U, EMB, MSK>, dim3(bwd_vblocks(V), S), dim3(GT), 0, s, logits, gain, x, subj, mask, (int)C, (int)B, V, acc, e)
+#define VG_GAM_STATS_C(CMAX, U)                                                                      \
+    if (mask) { if (emb) VG_GAM_STATS(CMAX, U, true, true); else VG_GAM_STATS(CMAX, U, false, true); } \
+    else { if (emb) VG_GAM_STATS(CMAX, U, true, false); else VG_GAM_STATS(CMAX, U, false, false); }
+    if (C <= 8) { VG_GAM_STATS_C(8, 4) }
+    else { VG_GAM_STATS_C(16, 2) }
+#undef VG_GAM_STATS_C
+#undef VG_GAM_STATS
+    return vg_check_launch("gam_stats");
 }
 
 namespace {

@@ -5,7 +5,8 @@ After training -- or straight from a checkpoint with `--recons_only` -- the wrap
 (multsubj_reg_run_GP.py:79-92): `model.project_latent` (UMAP projection of the latent means on the HIP kernels of
 latent_projection.py: `<epoch>_temp.pdf` and `<epoch>_latent_projection.csv`), `model.plot_GPs` (per-covariate GP posterior
 CSVs), `recon.mk_single_volumes` (one NIfTI per volume and map) and `recon.mk_avg_maps(mk_motion_maps=True)` (subject and
-grand averages), all on the training set as the reference does.
+grand averages), all on the training set as the reference does.  With `--stat_maps` (an extension) `recon.mk_stat_maps` follows:
+voxel-wise standard deviations, second-level t maps and variance-explained maps in a directory of their own.
 
 Multi-GPU: launch with torch.distributed.run, one process per GPU; the wrapper picks up RANK / LOCAL_RANK / WORLD_SIZE,
 `--batch-size` stays the GLOBAL minibatch and every rank draws its own slice of it (dp.ShardedBatchSampler); checkpoints
@@ -66,6 +67,10 @@ def build_parser():
                         help='(extension) Brain mask of --img_shape (.nii, .nii.gz or .npy; nonzero = in-brain; the first volume of a 4-D '
                              'file).  The log-likelihood and the GLM distance sum over the voxels of the mask only, and every exported map '
                              'is 0 outside it.  Default: every voxel counts, as the reference.')
+    parser.add_argument('--stat_maps', type=str2bool, nargs='?', const=True, default=False,
+                        help='(extension) After the averages, also write voxel-wise statistics under reconstructions/<ckpt>_stat_model_recons/: '
+                             'per subject <map>_std.nii, r2.nii and <covariate map>_partial_r2.nii, at top level <map>_t.nii and r2_avg.nii '
+                             '(one more pass over the training set; sums kept on the GPU).  Default: off.')
     return parser
 
 
@@ -187,6 +192,8 @@ def export_outputs(model, loaders_dict, args, dp=None):
         model.plot_GPs(csv_file=args.train_csv, save_dir=args.save_dir)
         recon.mk_single_volumes(loaders_dict['UnShuffled_train'], model, args.train_csv, args.save_dir)
         recon.mk_avg_maps(args.train_csv, model, args.save_dir, mk_motion_maps=True)
+        if getattr(args, 'stat_maps', False):
+            recon.mk_stat_maps(args.train_csv, model, args.save_dir, loaders_dict['UnShuffled_train'], mk_motion_maps=True)
     finally:
         model.dp = saved_dp
 

@@ -1170,6 +1170,30 @@ def gam_maps(logits, gain, x, eps, glm, nat=None, grid=None, mask=None):
     return maps
 
 
+def gam_stats_slots(C):
+    """Accumulator slots per subject and voxel of gam_stats_accumulate: 3C + 8 (slot table: include/vaegam.h)."""
+    return _lib.get_lib().size('vg_gam_stats_slots', int(C))
+
+
+def gam_stats_accumulate(logits, gain, x, subj, acc, nat=None, grid=None, mask=None):
+    """acc[s] += the per-voxel sums over the volumes b of this batch with subj[b] == s: first and second moments of the C+2 maps
+    (gam_maps' values, never materialised), of the data and of the residual, and the sums of (r + cons_i)^2 (vg_gam_stats_accumulate).
+    logits [C+1, B, V_grid], gain [C, B], x [B, V_nat] fp32; subj int32 [B]; acc float64 [S, 3C+8, V_nat], updated in place and
+    returned.  nat / grid / mask as gam_maps (without nat everything is on one grid).  One launch, no atomics: bit-reproducible.  A
+    subj entry outside [0, S) is skipped by the kernel; callers that want that refused check on the host."""
+    G, B, V = logits.shape
+    C = G - 1
+    if nat is None:
+        nat = grid = (1, 1, int(V))
+    Vn = int(nat[0]) * int(nat[1]) * int(nat[2])
+    assert V == int(grid[0]) * int(grid[1]) * int(grid[2]) and x.shape == (B, Vn) and subj.shape == (B,) and (C == 0 or gain.shape == (C, B))
+    assert acc.dim() == 3 and acc.shape[1] == 3 * C + 8 and acc.shape[2] == Vn
+    _call(x, 'vg_gam_stats_accumulate', _p(_chk(logits.contiguous())), _p(_chk(gain.contiguous())) if C > 0 else None, _p(_chk(x.contiguous())),
+          _p(_chk(subj, torch.int32)), None if mask is None else _p(_chk_mask(mask, Vn, x)), C, B, int(acc.shape[0]), _i3(nat), _i3(grid),
+          _p(_chk(acc, torch.float64)))
+    return acc
+
+
 class CholeskyF64(torch.autograd.Function):
     """L = chol(A) for a batch of small float64 SPD matrices (vg_cholesky_f64; n <= 128).  Backward is the
     standard  dA = sym( L^-T  Phi(L^T dL)  L^-1 )  with two triangular solves (rocBLAS trsm, capturable)."""

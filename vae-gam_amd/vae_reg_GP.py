@@ -998,6 +998,58 @@ class VAE(nn.Module):
         self.recon_sums = (sums, counts)
         return sums, counts
 
+    def _accumulate_statistics(self, out, x, ids, acc, counts):
+        """the accumulate step of map_statistics for one batch: out = forward_core's dict (logits, task_var), ids already checked"""
+        B = int(x.shape[0])
+        emb = (self.img_shape, self.grid_shape) if (self._embedded or self.mask is not None) else (None, None)
+        idl = ids.reshape(-1).long()
+        counts.index_add_(0, idl, torch.ones_like(idl, dtype=torch.float64))
+        ops.gam_stats_accumulate(out['logits'], out['task_var'], x.float().reshape(B, self.img_dim), idl.to(torch.int32), acc,
+                                 *emb, mask=self.mask)
+
+    def map_statistics(self, loader, num_subjects=None, noise=None, at_mean=False):
+        """Voxel-wise first and second moments of every map, of the data and of the residual, per subject (an extension; -> a
+        map_statistics.MapStatistics).  Per batch: forward_core without maps, then ONE launch (ops.gam_stats_accumulate) that reads
+        the logits once and adds each subject's partial sums to its accumulators -- no map tensor is materialised, no atomics, the
+        same bits on every run.  num_subjects: the subject slots (ids 0..S-1); None: as many as the largest id seen needs.
+        `noise` as in reconstruct; at_mean=True feeds zero-filled noise of draw_noise's shapes instead: the maps at the posterior
+        means, fully deterministic.  An id outside the range raises ValueError before that batch launches anything."""
+        from .map_statistics import MapStatistics
+        if at_mean and noise is not None:
+            raise ValueError('map_statistics: at_mean=True draws no noise; pass one of at_mean and noise')
+        C = self.num_covariates
+        keys = ['base'] + [c.img_key for c in self.schema] + ['full_rec']
+        K = ops.gam_stats_slots(C)
+        S = 0 if num_subjects is None else int(num_subjects)
+        if num_subjects is not None and S < 1:
+            raise ValueError('map_statistics: num_subjects must be at least 1, got %r' % (num_subjects,))
+        acc = torch.zeros(S, K, self.img_dim, device=self.device, dtype=torch.float64)
+        counts = torch.zeros(S, device=self.device, dtype=torch.float64)
+        with torch.no_grad():
+            for bi, sample in enumerate(loader):
+                idh = [int(v) for v in sample['subjid'].reshape(-1).tolist()]
+                lo, hi = min(idh), max(idh)
+                if lo < 0 or (num_subjects is not None and hi >= S):
+                    raise ValueError('map_statistics: batch %d holds the subject id %d, outside [0, %s)'
+                                     % (bi, lo if lo < 0 else hi, S if num_subjects is not None else 'inf'))
+                if hi >= S:                                                 # num_subjects=None: grow to the largest id seen
+                    acc = torch.cat([acc, torch.zeros(hi + 1 - S, K, self.img_dim, device=self.device, dtype=torch.float64)])
+                    counts = torch.cat([counts, torch.zeros(hi + 1 - S, device=self.device, dtype=torch.float64)])
+                    S = hi + 1
+                ids, covariates, x = self._batch_to_device(sample)
+                B = int(x.shape[0])
+                if at_mean:
+                    Bg = B if self.dp is None else B * self.dp.world_size
+                    nz = {'eps_w': torch.zeros(Bg, 1, device=x.device), 'eps_d': torch.zeros(Bg, self.num_latents, device=x.device),
+                          'eps_beta': torch.zeros(C, Bg, device=x.device)}
+                else:
+                    nz = None if noise is None else noise(bi, B)
+                out = self.forward_core(covariates, x, noise=nz, want_maps=False)
+                self._accumulate_statistics(out, x, ids, acc, counts)
+        if S == 0:
+            raise ValueError('map_statistics: the loader gave no batch and num_subjects was not given')
+        return MapStatistics(acc, counts, keys, tuple(self.img_shape))
+
     def plot_GPs(self, csv_file='', save_dir=''):
         """The CSV part of the reference's plot_GPs (vae_reg_GP.py:641-673): for every continuous covariate one
         `<epoch>_GP_<name>_full.csv` with the data set's covariate values sorted ascending and the posterior gain mean
