@@ -343,7 +343,7 @@ int vg_latent_bwd(const float* mu, const float* w, const float* d, const float* 
                   float* g_mu, float* g_w, float* g_a, void* stream);
 
 /* ELBO assembly (vae_reg_GP.py:406-410): loss[0] = c_kl*sum kl[B] + c_slp*sum slp[B] + c_gp*gp_kl[0] + c_dist*sum dist[CB];
- * backward writes the four constant gradients scaled by g_loss[0]. */
+ * backward writes the four constant gradients scaled by g_loss[0].  CB = 0 (no covariates): dist / g_dist may be null. */
 int vg_loss_fwd(const float* kl, const float* slp, const float* dist, const float* gp_kl, int32_t B, int32_t CB,
                 double c_kl, double c_slp, double c_gp, double c_dist, float* loss, void* stream);
 int vg_loss_bwd(const float* g_loss, int32_t B, int32_t CB, double c_kl, double c_slp, double c_gp, double c_dist,

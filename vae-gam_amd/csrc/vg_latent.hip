@@ -134,7 +134,7 @@ extern "C" int vg_latent_bwd(const float* mu, const float* w, const float* d, co
 
 extern "C" int vg_loss_fwd(const float* kl, const float* slp, const float* dist, const float* gp_kl, int32_t B, int32_t CB,
                            double c_kl, double c_slp, double c_gp, double c_dist, float* loss, void* stream) {
-    if (!kl || !slp || !dist || !gp_kl || !loss || B <= 0 || CB < 0) { vg_set_error("vg_loss_fwd: bad argument"); return VG_ERR_ARG; }
+    if (!kl || !slp || (CB > 0 && !dist) || !gp_kl || !loss || B <= 0 || CB < 0) { vg_set_error("vg_loss_fwd: bad argument"); return VG_ERR_ARG; }
     vg_launch(loss_fwd_k, dim3(1), dim3(256), 0, (hipStream_t)stream, kl, slp, dist, gp_kl, (int)B, (int)CB, (float)c_kl,
               (float)c_slp, (float)c_gp, (float)c_dist, loss);
     return vg_check_launch("loss_fwd");
@@ -142,7 +142,7 @@ extern "C" int vg_loss_fwd(const float* kl, const float* slp, const float* dist,
 
 extern "C" int vg_loss_bwd(const float* g_loss, int32_t B, int32_t CB, double c_kl, double c_slp, double c_gp, double c_dist,
                            float* g_kl, float* g_slp, float* g_dist, float* g_gp, void* stream) {
-    if (!g_loss || !g_kl || !g_slp || !g_dist || !g_gp || B <= 0 || CB < 0) { vg_set_error("vg_loss_bwd: bad argument"); return VG_ERR_ARG; }
+    if (!g_loss || !g_kl || !g_slp || (CB > 0 && !g_dist) || !g_gp || B <= 0 || CB < 0) { vg_set_error("vg_loss_bwd: bad argument"); return VG_ERR_ARG; }
     vg_launch(loss_bwd_k, dim3(1), dim3(256), 0, (hipStream_t)stream, g_loss, (int)B, (int)CB, (float)c_kl, (float)c_slp,
               (float)c_gp, (float)c_dist, g_kl, g_slp, g_dist, g_gp);
     return vg_check_launch("loss_bwd");
