@@ -67,6 +67,13 @@ int vg_tconv3d_s2_stats(const vg_conv_desc* d, const float* x, const float* wpk,
                         const float* in_scale, const float* in_shift, float* y, int32_t stats_per_group,
                         int32_t stats_relu, double* stats_part, void* stream);
 
+/* The partials vg_tconv3d_s2_stats would have written for the layer `d`, taken from its output y alone (d: N, CO, OD/OH/OW, pad_*,
+ * relu_out are read): the same thread mapping, summation order and chunk layout, so they are bit for bit the fused launch's whatever
+ * kernel produced y.  For a y that vg_conv_mm computed (same values, another reduction order in its own partials): the consuming
+ * batch norm then sees exactly the statistics of the register-tiled engine.  stats_relu = 0 on a rectified y is VG_ERR_ARG. */
+int vg_tconv3d_s2_stats_of(const vg_conv_desc* d, const float* y, int32_t stats_per_group, int32_t stats_relu,
+                           double* stats_part, void* stream);
+
 /* What vg_corr3d / vg_tconv3d_s2 (stats_per_group > 0: vg_tconv3d_s2_stats) would launch for the descriptor: nothing is launched and no
  * tensor memory is touched.  The record comes from the launchers' own planners, at the point where they would launch.
  * has_prologue: the launch would be given in_scale / in_shift (d->relu_in is read from the descriptor); a mask_src changes no choice.
@@ -104,7 +111,9 @@ int vg_tconv3d_s2_plan(const vg_conv_desc* d, int32_t has_prologue, int32_t stat
  *   (pd*sdo + od0[q], ph*sho + oh0[q], pw*swo + ow0[q] + replica).
  *   Block (bd, bh) of a sample works on position planes [bd*PD, +PD) x rows [bh*PHB, +PHB) and stages, cc channels at a time, the rows
  *   [bh*PHB*shi + hlo, ...+ (PHB-1)*shi + hhi] of input planes [bd*PD*sdi + d0, + LD) (LDS-DMA, one contiguous span per plane; dbuf: double-buffered).
- * bias / in_scale / in_shift / mask_src / stats_*: as vg_corr3d / vg_tconv3d_s2_stats (stats chunks: vg_conv_mm_stats_chunks). */
+ * bias / in_scale / in_shift / mask_src / stats_*: as vg_corr3d / vg_tconv3d_s2_stats (stats chunks: vg_conv_mm_stats_chunks).
+ * co_tot: 16 output channels of a stride-2 transposed conv have no free replica rows for the column pair, so such a layer runs as two
+ *   halves of CO = 8 channels through the 4-class path (co_tot = 16); co_tot / CO must be 1, or 2 with CO == 8 (else VG_ERR_ARG). */
 typedef struct vg_mm_desc {
     int32_t N, CI, CO;
     int32_t ID, IH, IW, OD, OH, OW;
@@ -118,6 +127,9 @@ typedef struct vg_mm_desc {
     int32_t hlo, hhi;          /* smallest / largest row offset dh in the window-offset table: which input rows a row slab stages */
     int32_t waves;             /* wavefronts per workgroup: 8 or 4 (4: half the tile, twice the co-resident workgroups per CU) */
     int32_t relu_out;          /* as vg_conv_desc.relu_out */
+    int32_t co_tot;            /* channels of y, mask_src and the statistics; 0 = CO.  2 * CO (CO == 8 only): the launch runs the layer as
+                                  two channel halves -- a_img holds the halves' images back to back, a block of the grid owns channels
+                                  [8h, 8h + 8); the partials are laid out as for CO = co_tot */
 } vg_mm_desc;
 int64_t vg_conv_mm_stats_chunks(const vg_mm_desc* d, int32_t stats_per_group);
 int vg_conv_mm(const vg_mm_desc* d, const float* x, const float* a_img, const int32_t* tau, const int32_t* dlt, const float* bias,

@@ -1,5 +1,8 @@
-"""Sweep conv_mm's tile choice (PD planes per block, cc channels per chunk) for one launch:  python tools/diag/mm_sweep.py B C layer:dir [lib]
-Prints us per launch for every (PD, cc) the kernel accepts, with LDS bytes and blocks per CU the occupancy query reports."""
+"""Sweep conv_mm's tile choice (waves, PD planes per block, PHB rows, cc channels per chunk, buffers) for one launch:
+  [VG_IMG=82x98x70] python tools/diag/mm_sweep.py B C layer:dir ...
+Prints us per launch for every tile the planner accepts, and first the register-tiled kernel's time for the same launch.  The
+forward of a layer that feeds a batch norm without one on its own input (convt2, convt4) is launched as the train step launches
+it: no prologue, statistics partials, stored rectified."""
 import ctypes, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
@@ -9,7 +12,7 @@ import vae_gam_amd
 from vae_gam_amd import ops, _lib
 from vae_gam_amd.schema import net_geometry
 B, C = int(sys.argv[1]), int(sys.argv[2])
-geom = net_geometry((41, 49, 35))
+geom = net_geometry(tuple(int(v) for v in os.environ.get('VG_IMG', '41x49x35').split('x')))
 dev = 'cuda'
 
 
@@ -40,10 +43,20 @@ for item in sys.argv[3:]:
     print('%s: default PD %d cc %d tpc %d' % (item, base.PD, base.cc, base.tpc))
     ci = base.CI
     aimg0 = base.gather(w)
+    step_like = name in ('convt2', 'convt4')
     if direction == 'fwd':
-        ref = ops.conv_mm(x, base, aimg0, b, True, sc, sh, B, None, None)
+        run = (lambda pl, a: ops.conv_mm(x, pl, a, b, False, None, None, 1, None, B, True)[0]) if step_like else \
+            (lambda pl, a: ops.conv_mm(x, pl, a, b, True, sc, sh, B, None, None))
+        wf = ops.pack_weight(w, sp, 'fwd')
+        direct = (lambda: ops.conv_forward(x, wf, b, sp, False, None, None, 1, B, True)) if step_like else \
+            (lambda: ops.conv_forward(x, wf, b, sp, True, sc, sh, B))
     else:
-        ref = ops.conv_mm(dy, base, aimg0, None, False, None, None, 1, x)
+        run = lambda pl, a: ops.conv_mm(dy, pl, a, None, False, None, None, 1, x)
+        wb = ops.pack_weight(w, sp, 'bwd')
+        direct = lambda: ops.conv_backward_data(dy, wb, sp, sizes[i], x)
+    ref = run(base, aimg0)
+    print('  register-tiled kernel %8.1f us    default tile (W %d PD %d PHB %d cc %d db %d) %8.1f us' % (
+        timeit(direct, 20), base.waves, base.PD, base.PHB, base.cc, base.dbuf, timeit(lambda: run(base, aimg0), 20)), flush=True)
     shi = base.shi
     for W in (8, 4):
       for PD in range(1, 9):
@@ -57,14 +70,11 @@ for item in sys.argv[3:]:
                 if pl is None:
                     continue
                 aimg = pl.gather(w)
-                if direction == 'fwd':
-                    fn = lambda: ops.conv_mm(x, pl, aimg, b, True, sc, sh, B, None, None)
-                else:
-                    fn = lambda: ops.conv_mm(dy, pl, aimg, None, False, None, None, 1, x)
+                fn = lambda: run(pl, aimg)
                 try:
                     out = fn()
                     err = float((out - ref).abs().max())
-                    t = timeit(fn, 5)
+                    t = timeit(fn, 10)
                 except Exception as e:
                     print('  W %d PD %d PHB %d cc %d db %d: %s' % (W, PD, PHB, cc, dbuf, str(e)[:80])); continue
                 print('  W %d PD %d PHB %2d cc %2d db %d tpc %d  %8.1f us   maxdiff %.2e' % (W, PD, PHB, cc, dbuf, pl.tpc, t, err), flush=True)

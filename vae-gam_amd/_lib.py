@@ -32,7 +32,7 @@ class MmDesc(ctypes.Structure):
     _fields_ = [(n, i32) for n in ('N', 'CI', 'CO', 'ID', 'IH', 'IW', 'OD', 'OH', 'OW', 'nq')] + [('ks', i32 * 4)] + \
                [(n, i32) for n in ('PDT', 'PH', 'PW', 'PD', 'sdi', 'shi', 'swi', 'd0', 'LD', 'cc', 'sdo', 'sho', 'swo')] + \
                [('od0', i32 * 4), ('oh0', i32 * 4), ('ow0', i32 * 4)] + [(n, i32) for n in ('relu_in', 'per_group', 'tpc', 'slack', 'dbuf', 'PHB', 'hlo', 'hhi', 'waves',
-                                                                                         'relu_out')]
+                                                                                         'relu_out', 'co_tot')]
 
 
 class GainDesc(ctypes.Structure):
@@ -64,6 +64,7 @@ _PROTOS = {
     'vg_tconv3d_s2': (ctypes.c_int, [ctypes.POINTER(ConvDesc), vp, vp, vp, vp, vp, vp, vp, vp]),
     'vg_tconv3d_s2_stats_chunks': (i64, [ctypes.POINTER(ConvDesc), i32]),
     'vg_tconv3d_s2_stats': (ctypes.c_int, [ctypes.POINTER(ConvDesc), vp, vp, vp, vp, vp, vp, i32, i32, vp, vp]),
+    'vg_tconv3d_s2_stats_of': (ctypes.c_int, [ctypes.POINTER(ConvDesc), vp, i32, i32, vp, vp]),
     'vg_corr3d_plan': (ctypes.c_int, [ctypes.POINTER(ConvDesc), i32, ctypes.POINTER(i32), i32]),
     'vg_tconv3d_s2_plan': (ctypes.c_int, [ctypes.POINTER(ConvDesc), i32, i32, ctypes.POINTER(i32), i32]),
     'vg_bn_stats_from_parts': (ctypes.c_int, [vp, i32, i32, i64, f64, vp, vp, f32, vp, vp, vp, vp, vp, vp, vp]),

@@ -775,11 +775,70 @@ tconv3d_s2_k(const float* __restrict__ x, const float* __restrict__ wpk, const f
     }
 }
 
-template <int COT, int KD, int KH, int KW, int COC = 0>
-int launch_tconv(const vg_conv_desc* d, const float* x, const float* wpk, const float* bias, const float* in_scale,
-                 const float* in_shift, const float* mask_src, float* y, hipStream_t s,
-                 double* stats_part = nullptr, int stats_relu = 0, int stats_pg = 1, const ConvQuery* query = nullptr) {
-    TconvParams p; p.d = *d;
+// The statistics partials vg_tconv3d_s2_stats writes beside y, from y alone: the same thread -> outputs mapping, the same order of
+// every fp32 sum (thread: rd, rh, channel, rw; wavefront: xor 32 .. 1) and the same chunk layout, so the partials are bit for bit
+// those of the fused launch whichever kernel produced y (vg_conv_mm sums a lane's elements in another order: its own partials
+// differ from these in the last bit of a few sums).  y holds o, or max(o, 0) where it was stored rectified: max(y, 0) is h either way.
+template <int COT>
+__global__ void __launch_bounds__(256, 4)
+tconv_stats_of_k(const float* __restrict__ y, TconvParams p, double* __restrict__ stats_part, int stats_relu, int stats_pg) {
+    const vg_conv_desc& d = p.d;
+    const int tid = threadIdx.x;
+    const int n = blockIdx.y;
+    int tile = blockIdx.x;
+    const int twi = tile % p.tilesW; tile /= p.tilesW;
+    const int thi = tile % p.tilesH; const int tdi = tile / p.tilesH;
+    const int CO = d.CO;
+    const int co0 = blockIdx.z * COT;
+    const int jwl = tid % p.TJW; const int jhl = (tid / p.TJW) % p.TJH; const int jdl = tid / (p.TJW * p.TJH);
+    const int jd = tdi * p.TJD + jdl, jh = thi * p.TJH + jhl, jw = twi * p.TJW + jwl;
+    const bool active = !(jdl >= p.TJD || jd >= p.JD || jh >= p.JH || jw >= p.JW);   // (the others add zeros to their wavefront's sums)
+    const size_t plane = (size_t)d.OH * d.OW;
+    float st_s[COT], st_q[COT];
+#pragma unroll
+    for (int co = 0; co < COT; ++co) { st_s[co] = 0.f; st_q[co] = 0.f; }
+#pragma unroll
+    for (int rd = 0; rd < 2; ++rd) {
+        const int od = 2 * jd + rd - d.pad_d;
+        if (!active || od < 0 || od >= d.OD) continue;
+#pragma unroll
+        for (int rh = 0; rh < 2; ++rh) {
+            const int oh = 2 * jh + rh - d.pad_h;
+            if (oh < 0 || oh >= d.OH) continue;
+#pragma unroll
+            for (int co = 0; co < COT; ++co) {
+                const size_t base = (((size_t)n * CO + co0 + co) * d.OD + od) * plane + (size_t)oh * d.OW;
+                const int ow0 = 2 * jw - d.pad_w;
+#pragma unroll
+                for (int rw = 0; rw < 2; ++rw) {
+                    if (ow0 + rw >= 0 && ow0 + rw < d.OW) {
+                        const float o = y[base + ow0 + rw];
+                        const float h = stats_relu ? vg_max(o, 0.f) : o;
+                        st_s[co] += h; st_q[co] = fmaf(h, h, st_q[co]);
+                    }
+                }
+            }
+        }
+    }
+    const int lane = tid % VG_WAVE, wv = tid / VG_WAVE, nw = blockDim.x / VG_WAVE;
+    const int g = n / stats_pg;
+    const size_t chunks = (size_t)stats_pg * gridDim.x * nw;
+    const size_t chunk = ((size_t)(n % stats_pg) * gridDim.x + blockIdx.x) * nw + wv;
+#pragma unroll
+    for (int co = 0; co < COT; ++co) {
+        float a = st_s[co], b = st_q[co];
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) { a += __shfl_xor(a, off); b += __shfl_xor(b, off); }
+        if (lane == 0) {
+            double* dst = stats_part + (((size_t)g * CO + co0 + co) * chunks + chunk) * 2;
+            dst[0] = (double)a; dst[1] = (double)b;
+        }
+    }
+}
+
+// threads of a block and the tiling of the 2x2x2 bricks: the same for every instance (the statistics chunks depend on nothing else)
+static int tconv_geometry(const vg_conv_desc* d, TconvParams* pp) {
+    TconvParams& p = *pp; p.d = *d;
     p.JD = (d->OD + d->pad_d + 1) / 2; p.JH = (d->OH + d->pad_h + 1) / 2; p.JW = (d->OW + d->pad_w + 1) / 2;
     p.TJW = p.JW < 32 ? p.JW : 32;
     int rem = 256 / p.TJW;
@@ -788,8 +847,16 @@ int launch_tconv(const vg_conv_desc* d, const float* x, const float* wpk, const 
     p.TJD = p.JD < rem ? p.JD : rem;
     if (p.TJD < 1) p.TJD = 1;
     p.tilesW = vg_cdiv(p.JW, p.TJW); p.tilesH = vg_cdiv(p.JH, p.TJH); p.tilesD = vg_cdiv(p.JD, p.TJD);
+    return vg_cdiv(p.TJW * p.TJH * p.TJD, VG_WAVE) * VG_WAVE;
+}
+
+template <int COT, int KD, int KH, int KW, int COC = 0>
+int launch_tconv(const vg_conv_desc* d, const float* x, const float* wpk, const float* bias, const float* in_scale,
+                 const float* in_shift, const float* mask_src, float* y, hipStream_t s,
+                 double* stats_part = nullptr, int stats_relu = 0, int stats_pg = 1, const ConvQuery* query = nullptr) {
+    TconvParams p;
+    const int threads = tconv_geometry(d, &p);
     if (d->CO % COT) { vg_set_error("tconv3d_s2: CO=%d not a multiple of %d", d->CO, COT); return VG_ERR_UNSUPPORTED; }
-    const int threads = vg_cdiv(p.TJW * p.TJH * p.TJD, VG_WAVE) * VG_WAVE;
     dim3 grid(p.tilesW * p.tilesH * p.tilesD, d->N, d->CO / COT);
     const bool nopro = in_scale == nullptr && !d->relu_in;
     if (query) {                                            // nothing is launched: the choices the launches below would use
@@ -965,4 +1032,22 @@ extern "C" int vg_tconv3d_s2_stats(const vg_conv_desc* d, const float* x, const 
     if (!stats_part || stats_per_group <= 0 || d->N % stats_per_group) { vg_set_error("vg_tconv3d_s2_stats: bad statistics arguments"); return VG_ERR_ARG; }
     return tconv_dispatch(d, x, wpk, bias, in_scale, in_shift, nullptr, y, (hipStream_t)stream, stats_part, stats_relu,
                           stats_per_group, nullptr);
+}
+
+extern "C" int vg_tconv3d_s2_stats_of(const vg_conv_desc* d, const float* y, int32_t stats_per_group, int32_t stats_relu,
+                                      double* stats_part, void* stream) {
+    if (!d || !y || !stats_part) { vg_set_error("vg_tconv3d_s2_stats_of: null argument"); return VG_ERR_ARG; }
+    if (d->N <= 0 || d->N > 65535 || d->CO <= 0 || d->OD <= 0 || d->OH <= 0 || d->OW <= 0 || d->pad_d < 0 || d->pad_h < 0 || d->pad_w < 0) {
+        vg_set_error("vg_tconv3d_s2_stats_of: bad shape N=%d CO=%d out=%dx%dx%d", d->N, d->CO, d->OD, d->OH, d->OW); return VG_ERR_ARG;
+    }
+    if (stats_per_group <= 0 || d->N % stats_per_group) { vg_set_error("vg_tconv3d_s2_stats_of: bad statistics arguments"); return VG_ERR_ARG; }
+    if (d->relu_out && !stats_relu) { vg_set_error("vg_tconv3d_s2_stats_of: a rectified tensor does not hold the pre-activation's statistics"); return VG_ERR_ARG; }
+    if (d->CO % 4) { vg_set_error("vg_tconv3d_s2_stats_of: CO=%d not a multiple of 4", d->CO); return VG_ERR_UNSUPPORTED; }
+    TconvParams p;
+    const int threads = tconv_geometry(d, &p);
+    const int cot = d->CO % 8 == 0 ? 8 : 4;
+    dim3 grid(p.tilesW * p.tilesH * p.tilesD, d->N, d->CO / cot);
+    if (cot == 8) vg_launch(tconv_stats_of_k<8>, grid, dim3(threads), 0, (hipStream_t)stream, y, p, stats_part, (int)stats_relu, (int)stats_per_group);
+    else vg_launch(tconv_stats_of_k<4>, grid, dim3(threads), 0, (hipStream_t)stream, y, p, stats_part, (int)stats_relu, (int)stats_per_group);
+    return vg_check_launch("tconv3d_s2_stats_of");
 }

@@ -39,7 +39,8 @@ constexpr int MM_ZPAD = 64;                // zero floats at the head of every c
 
 struct MmParams {
     vg_mm_desc d;
-    int bps, nsplit;                       // blocks per sample, sample splits (grid = bps * nsplit)
+    int bps, nsplit;                       // blocks per sample, sample splits (grid = bps * nsplit * nco)
+    int nco, cot;                          // channel halves (1, or 2: a block owns channels [CO*h, CO*h + CO) of cot = nco * CO), channels of y / mask_src / statistics
     int ksbase[MM_MAXQ], a_off[MM_MAXQ];   // first table row / first A-image float of class q
     int kstot, aimg_floats;
     int a_res;                             // 1: the whole A image stays in LDS; 0: the slices of the running channel chunk are staged with it
@@ -95,7 +96,11 @@ conv_mm_k(const float* __restrict__ x, const float* __restrict__ a_img, const in
     const int tid = threadIdx.x, lane = tid % VG_WAVE, wave = vg_wave_id();
     const int kk = lane >> 4, jl = lane & 15;
     // (an XCD-aware order -- the slabs of one sample on one XCD, so that they share the halo planes in its L2 -- measured neutral to 15 % slower)
-    const int b = blockIdx.x % p.bps, split = blockIdx.x / p.bps;
+    const int b = blockIdx.x % p.bps, bq = blockIdx.x / p.bps;
+    // channel half of this block (0 unless the layer runs as two halves of 8 channels): the halves of a (slab, split) pair sit next to
+    // each other in the grid; everything below that depends on it is a wave-uniform offset formed once
+    const int split = bq / p.nco, half = bq - split * p.nco, co_h = half * d.CO;
+    a_img += (size_t)half * p.aimg_floats;
     const int IHW = d.IH * d.IW, OHW = d.OH * d.OW;
     const int CI = d.CI, CO = d.CO;
     constexpr bool STATIC_K = K0 > 0;
@@ -196,7 +201,7 @@ conv_mm_k(const float* __restrict__ x, const float* __restrict__ a_img, const in
     float mreg[MASKED ? TPC : 1][4];                                     // ReLU mask source of the sample in flight (data gradients)
     vg_f2 bias_l[2];
 #pragma unroll
-    for (int r = 0; r < 2; ++r) { bias_l[r].x = bias ? bias[co_l + 2 * r] : 0.f; bias_l[r].y = bias ? bias[co_l + 2 * r + 1] : 0.f; }
+    for (int r = 0; r < 2; ++r) { bias_l[r].x = bias ? bias[co_h + co_l + 2 * r] : 0.f; bias_l[r].y = bias ? bias[co_h + co_l + 2 * r + 1] : 0.f; }
     int nact = 0;                                                        // tiles this wave owns (wave-uniform)
 #pragma unroll
     for (int i = 0; i < TPC; ++i) nact += (i * MM_W + wave < ntiles) ? 1 : 0;
@@ -214,7 +219,7 @@ conv_mm_k(const float* __restrict__ x, const float* __restrict__ a_img, const in
 
     // fetch the mask source of sample n's outputs (class 0) into registers; consumed by store_class
     auto load_mask = [&](int n) __attribute__((always_inline)) {
-        const char* mn = reinterpret_cast<const char*>(mask_src + (size_t)n * CO * ovol);
+        const char* mn = reinterpret_cast<const char*>(mask_src + ((size_t)n * p.cot + co_h) * ovol);
 #pragma unroll
         for (int i = 0; i < TPC; ++i) {
             const bool okt = i < nact && ((vbits >> i) & 1u);
@@ -234,8 +239,8 @@ conv_mm_k(const float* __restrict__ x, const float* __restrict__ a_img, const in
         constexpr bool STATS = decltype(stats_c)::value, SRELU = decltype(srelu_c)::value;
         const long long cq4 = 4ll * (d.od0[q] * OHW + d.oh0[q] * d.OW + d.ow0[q]);
         const size_t ovol4 = ovol * 4;
-        char* yq = reinterpret_cast<char*>(y + (size_t)n * CO * ovol) + cq4;
-        const char* mq = reinterpret_cast<const char*>(mask_src + (size_t)n * CO * ovol) + cq4;
+        char* yq = reinterpret_cast<char*>(y + ((size_t)n * p.cot + co_h) * ovol) + cq4;
+        const char* mq = reinterpret_cast<const char*>(mask_src + ((size_t)n * p.cot + co_h) * ovol) + cq4;
         float* yr[4]; const float* mr[4];
 #pragma unroll
         for (int r = 0; r < 4; ++r) { yr[r] = reinterpret_cast<float*>(yq + r * ovol4); mr[r] = reinterpret_cast<const float*>(mq + r * ovol4); }
@@ -318,7 +323,7 @@ conv_mm_k(const float* __restrict__ x, const float* __restrict__ a_img, const in
             for (int off = 8; off > 0; off >>= 1) { sa += __shfl_xor(sa, off); sb += __shfl_xor(sb, off); }
             if (CO == 8) { sa += __shfl_xor(sa, 32); sb += __shfl_xor(sb, 32); }   // the two replicas of a channel
             if (jl == 0 && (CO == 16 || kk < 2)) {
-                double* dst = stats_part + (((size_t)g * CO + co_l + r) * chunks + chunkid) * 2;
+                double* dst = stats_part + (((size_t)g * p.cot + co_h + co_l + r) * chunks + chunkid) * 2;
                 dst[0] = (double)sa; dst[1] = (double)sb;
             }
         }
@@ -523,6 +528,11 @@ static int mm_plan_params(const vg_mm_desc* d, MmParams* p, size_t* shmem, const
         vg_set_error("%s: bad descriptor", who); return VG_ERR_ARG;
     }
     p->d = *d;
+    p->cot = d->co_tot ? d->co_tot : d->CO;
+    p->nco = p->cot / d->CO;
+    if (p->cot <= 0 || p->cot % d->CO || p->nco > 2 || (p->nco == 2 && d->CO != 8)) {
+        vg_set_error("%s: co_tot = %d with CO = %d: a launch covers CO channels, or two halves of 8", who, d->co_tot, d->CO); return VG_ERR_ARG;
+    }
     int row = 0, af = 0;
     for (int q = 0; q < d->nq; ++q) {
         if (d->ks[q] <= 0 || d->ks[q] > 32) { vg_set_error("%s: k-steps per channel must be 1..32 (class %d: %d)", who, q, d->ks[q]); return VG_ERR_ARG; }
@@ -576,13 +586,13 @@ extern "C" int vg_conv_mm(const vg_mm_desc* d, const float* x, const float* a_im
     p.has_pro = (d->relu_in || in_scale) ? 1 : 0;
     hipStream_t s = (hipStream_t)stream;
     // persistent grid = the blocks that are resident at once (occupancy query of the chosen instance x 256 CUs), dealt over the
-    // bps position slabs of a sample: every further block of a slab takes every nsplit-th sample
+    // bps position slabs (x nco channel halves) of a sample: every further block of a slab takes every nsplit-th sample
     const int threads = d->waves * VG_WAVE;
     auto launch = [&](auto kernel) {
         const int bpc = vg_blocks_per_cu((const void*)kernel, threads, shmem);
-        int ns = (256 * bpc) / p.bps; if (ns < 1) ns = 1; if (ns > d->N) ns = d->N;
+        int ns = (256 * bpc) / (p.bps * p.nco); if (ns < 1) ns = 1; if (ns > d->N) ns = d->N;
         p.nsplit = ns;
-        vg_launch(kernel, dim3(p.bps * p.nsplit), dim3(threads), shmem, s, x, a_img, (const int*)tau, (const int*)dlt, bias, in_scale, in_shift,
+        vg_launch(kernel, dim3(p.bps * p.nsplit * p.nco), dim3(threads), shmem, s, x, a_img, (const int*)tau, (const int*)dlt, bias, in_scale, in_shift,
                   mask_src, y, stats_part, (int)(stats_part ? stats_per_group : 1), (int)stats_relu, p);
     };
     const bool db = d->dbuf != 0, mk = mask_src != nullptr, w4 = d->waves == 4;

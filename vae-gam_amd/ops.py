@@ -610,7 +610,8 @@ class BnConvAct(torch.autograd.Function):
                 scale, shift, mean, rstd = bn_stats(p_in, gamma, beta, relu_in, per_group, sync, pre_stats)
             mmf = _mm_for(packed, weight, spec, 'fwd', tuple(p_in.shape[2:]), None)
             if mmf is not None:
-                y = conv_mm(p_in, mmf[0], mmf[1], bias, fwd_relu, scale, shift, per_group, None, next_bn, relu_out)
+                y = conv_mm(p_in, mmf[0], mmf[1], bias, fwd_relu, scale, shift, per_group, None, next_bn, relu_out,
+                            stats_like=spec if mmf[0].co_blk != mmf[0].CO else None)
             else:
                 wf = packed.get(spec.name, 'fwd') if packed is not None else pack_weight(weight, spec, 'fwd')
                 y = conv_forward(p_in, wf, bias, spec, fwd_relu, scale, shift, per_group, next_bn, relu_out)
@@ -728,6 +729,20 @@ class BnConvAct(torch.autograd.Function):
 _MM_SKIP = set(filter(None, _os.environ.get('VG_MM_SKIP', '').split(',')))
 
 
+def _halves_win(plan):
+    """The 16-channel stride-2 transposed convs, run as two halves of 8 channels (mm_plan).  MI355X, tools/diag/mm_sweep.py, us,
+    register-tiled kernel -> matrix-core kernel at the planner's tile (launched as the step launches them: convt2 forward without
+    prologue, with statistics, stored rectified; conv4's data gradient masked):
+      41x49x35, 576 / 64 samples:  convt2 fwd  247 ->  138 (two blocks of 5 / 4 position planes per sample and half);  conv4 bwd 33.8 -> 31.7
+      82x98x70, 832 / 64 samples:  convt2 fwd 3214 -> 1619 (one position plane per block);                            conv4 bwd  325 ->  192
+      21x21x21, 576 / 64 samples:  convt2 fwd 25.4 -> 30.6;  conv4 bwd 14.6 -> 15.8 -- a block holds a whole sample's half there: 4
+        tiles per wave at most behind a 20 KB A image and one input copy, nothing to overlap them with.  Declined.
+    In the step convt2's forward is followed by vg_tconv3d_s2_stats_of (conv_mm(stats_like=...): statistics bit-equal to the
+    register-tiled engine's); bench.py --kernel-table, ms: 0.2435 -> 0.1255 + 0.0696; conv4 bwd 0.0464 -> 0.0338."""
+    nslab = (plan.PH + plan.PHB - 1) // plan.PHB
+    return ((plan.PDT + plan.PD - 1) // plan.PD) * nslab > 1
+
+
 def mm_wins(plan):
     """Where vg_conv_mm is the faster (or an equally fast) engine -- MI355X, tools/layer_bench.py at batch 64 / 8 covariates, us,
     register-tiled kernel -> matrix-core kernel:
@@ -737,12 +752,17 @@ def mm_wins(plan):
       the 3x3x3 stride-1 layers with 8 <-> 16 channels (convt3 fwd 520-534 -> 516, bwd 442-446 -> 444; conv3): ties -- taken, so
       that the matrix cores carry every launch that is a real contraction and the register-tiled kernels keep the 1-channel ends.
     Kept on the register-tiled kernels: stride-2 correlations (convt4's data gradient 574 vs 714: one input channel fills the
-    LDS budget, a unit is 57 MFMAs per wave between barriers; conv2 / conv4 forward)."""
+    LDS budget, a unit is 57 MFMAs per wave between barriers; conv2 / conv4 forward).
+    The 16-channel stride-2 transposed convs (convt2 forward, conv4's data gradient), two channel halves: _halves_win."""
     if plan is None:
         return False
     if _MM_SKIP and 'k%d' % plan.ks[0] in _MM_SKIP and (plan.PDT + plan.PD - 1) // plan.PD > 1:     # tuning knob: VG_MM_SKIP=k7,k9 -> those go register-tiled
         return False
-    if USE_MM >= 2 or (plan.PDT + plan.PD - 1) // plan.PD == 1:
+    if USE_MM >= 2:
+        return True
+    if plan.co_blk != plan.CO:
+        return _halves_win(plan)
+    if (plan.PDT + plan.PD - 1) // plan.PD == 1:
         return True
     if plan.mode == 'tconv':
         return list(plan.ks) in ([3, 2, 2, 1], [2, 1, 1, 1], [2, 2, 2, 2])
@@ -1412,6 +1432,9 @@ _MM_TUNED = {
     ('corr', 1, 8, 16, (3, 3, 3), (19, 23, 16), (17, 21, 14)): (8, 1, 21, 8, 0),  # conv3 forward 46 (score's choice, a 6-row slab: 51)
     ('corr', 1, 8, 16, (3, 3, 3), (18, 23, 16), (16, 21, 14)): (8, 2, 11, 8, 1),  # convt3 data gradient 242 (whole planes: 254)
     ('tconv', 2, 8, 8, (5, 3, 3), (18, 23, 16), (39, 47, 33)): (8, 2, 12, 8, 1),   # convt4 forward 610 (whole planes, single buffer: 656 in the same run)
+    # two channel halves (the score's choices; the runners-up of the sweep behind them)
+    ('tconv', 2, 16, 16, (3, 3, 3), (8, 10, 7), (16, 21, 14)): (8, 5, 11, 16, 0),  # convt2 forward 138-142 (3 planes, double-buffered: 158; 4-wave blocks of 2 planes: 166)
+    ('tconv', 2, 16, 16, (3, 3, 3), (18, 22, 15), (37, 45, 31)): (8, 1, 23, 16, 0),  # 82x98x70 convt2 forward 1619-1686 (4 planes x 8-row slabs: 1747; double-buffered: 1856)
 }
 _MM_WAVES = 8
 
@@ -1419,7 +1442,8 @@ _MM_WAVES = 8
 class MmPlan:
     """Host-side description of one conv / transposed-conv launch for vg_conv_mm (include/vaegam.h): position grid, staging
     geometry and the window-offset tables, plus `aidx` -- for every A-image slot the index of the weight it holds inside the
-    layer's own weight tensor (-1 = zero)."""
+    layer's own weight tensor (-1 = zero).  CO: channels of y; co_blk: channels a block computes (CO, or 8 of 16: two halves, whose
+    images sit back to back in `aidx`)."""
 
     def __init__(self, **kw):
         self.__dict__.update(kw)
@@ -1433,10 +1457,11 @@ class MmPlan:
 
     def desc(self, N, relu_in, per_group, relu_out=False):
         d = _lib.MmDesc()
-        for k in ('CI', 'CO', 'ID', 'IH', 'IW', 'OD', 'OH', 'OW', 'nq', 'PDT', 'PH', 'PW', 'PD', 'sdi', 'shi', 'swi', 'd0', 'LD', 'cc', 'sdo', 'sho',
+        for k in ('CI', 'ID', 'IH', 'IW', 'OD', 'OH', 'OW', 'nq', 'PDT', 'PH', 'PW', 'PD', 'sdi', 'shi', 'swi', 'd0', 'LD', 'cc', 'sdo', 'sho',
                   'swo', 'tpc', 'slack', 'dbuf', 'PHB', 'hlo', 'hhi', 'waves'):
             setattr(d, k, int(getattr(self, k)))
         d.N, d.relu_in, d.per_group, d.relu_out = int(N), int(bool(relu_in)), int(per_group), int(bool(relu_out))
+        d.CO, d.co_tot = int(self.co_blk), int(self.CO)                 # channels per block (the matrix rows' channels), channels of y
         for q in range(4):
             d.ks[q] = int(self.ks[q]) if q < self.nq else 0
             d.od0[q] = int(self.od0[q]) if q < self.nq else 0
@@ -1487,8 +1512,9 @@ _MM_PLANS = {}
 
 
 def mm_plan(spec: ConvSpec, direction: str, in_size, out_size=None, force=None) -> Optional[MmPlan]:
-    """Plan for vg_conv_mm, or None when the launch is not covered (1-channel ends, 16-channel stride-2 transposed convs, shapes
-    that do not fit LDS): the caller then uses the register-tiled kernels.  `in_size`: spatial size of the tensor the launch READS
+    """Plan for vg_conv_mm, or None when the launch is not covered (1-channel ends, shapes that do not fit LDS): the caller then
+    uses the register-tiled kernels.  A stride-2 transposed conv with 16 output channels (forward of a convt layer with co == 16,
+    data gradient of a conv layer with ci == 16) is planned as two halves of 8 channels: plan.CO = 16, plan.co_blk = 8.  `in_size`: spatial size of the tensor the launch READS
     (the layer input for 'fwd', dy for 'bwd'); `out_size`: spatial size it writes (needed for 'bwd')."""
     import numpy as np
     key = (spec, direction, tuple(in_size), None if out_size is None else tuple(out_size), force)
@@ -1498,7 +1524,7 @@ def mm_plan(spec: ConvSpec, direction: str, in_size, out_size=None, force=None) 
     if osz is None:
         osz = tuple(out_size)
     plan = None
-    if CO in (8, 16) and CI >= 8 and not (mode == 'tconv' and CO != 8):
+    if CO in (8, 16) and CI >= 8:
         plan = _mm_build(mode, S, pad, CI, CO, K, tuple(in_size), tuple(osz), widx, force)
     _MM_PLANS[key] = plan
     return plan
@@ -1511,7 +1537,11 @@ def _mm_build(mode, S, pad, CI, CO, K, isz, osz, widx, force=None):
     ID, IH, IW = isz
     OD, OH, OW = osz
     IHW = IH * IW
-    NR = 16 // CO
+    # 16 output channels of a stride-2 transposed conv: the w-parity pair needs the two 8-row replicas, so the layer runs as two halves
+    # of 8 channels (a block of the grid owns one half: vg_mm_desc.co_tot), each through the 4-class plan of an 8-channel layer
+    nco = 2 if (mode == 'tconv' and CO == 16) else 1
+    CO_l = CO // nco
+    NR = 16 // CO_l
     classes = []                                   # per class: list of (dd, dh, dw, tap(rho) -> (kd, kh, kw) or None)
     if mode == 'corr':
         KWp = KW + (NR - 1) * S
@@ -1559,11 +1589,11 @@ def _mm_build(mode, S, pad, CI, CO, K, isz, osz, widx, force=None):
         return None
     rows = sum(ks)
     tau = np.zeros((rows, 4), np.int32); dlt = np.zeros((rows, 4, 3), np.int32)
-    aidx = []
+    aidx = [[] for _ in range(nco)]                # per channel half: the classes' images back to back
     slack = 0
     r0 = 0
     for q, ent in enumerate(classes):
-        a = -np.ones((CI, ks[q], 64), np.int32)
+        a = -np.ones((nco, CI, ks[q], 64), np.int32)
         for s in range(ks[q]):
             for kk in range(4):
                 kap = 4 * s + kk
@@ -1575,16 +1605,19 @@ def _mm_build(mode, S, pad, CI, CO, K, isz, osz, widx, force=None):
                 if kap >= len(ent):
                     continue
                 for row in range(16):
-                    rho, co = row // CO, row % CO
+                    rho, co = row // CO_l, row % CO_l
                     t = e[3](rho)
                     if t is None:
                         continue
                     lane = kk * 16 + row
-                    for ci in range(CI):
-                        a[ci, s, lane] = widx(ci, t[0], t[1], t[2], co)
-        aidx.append(a.reshape(-1))
+                    for h in range(nco):
+                        for ci in range(CI):
+                            a[h, ci, s, lane] = widx(ci, t[0], t[1], t[2], co + CO_l * h)
+        for h in range(nco):
+            aidx[h].append(a[h].reshape(-1))
         r0 += ks[q]
-    aidx = np.concatenate(aidx)
+    aidx = np.concatenate([np.concatenate(a) for a in aidx])
+    aimg_blk = aidx.size // nco                    # what a block keeps in LDS: one half's image
     tpc_max = (8 if max(ks) <= 12 else 3) if nq == 1 else 4        # registers: one operand offset per (tile, k-step)
     hlo, hhi = int(dlt[:, :, 1].min()), int(dlt[:, :, 1].max())
     # Tile choice: a block = W waves on PD position planes x PHB position rows (x all PW columns).  Measured (tools/diag/mm_sweep.py,
@@ -1615,7 +1648,7 @@ def _mm_build(mode, S, pad, CI, CO, K, isz, osz, widx, force=None):
                     for dbuf in (1, 0):
                         if pin and (W, PD, PHB, cc, dbuf) != tuple(pin):
                             continue
-                        lds = (((aidx.size + 63) // 64) * 64 + rows * 64 + (1 + dbuf) * cc * CHP + 64) * 4
+                        lds = (((aimg_blk + 63) // 64) * 64 + rows * 64 + (1 + dbuf) * cc * CHP + 64) * 4
                         if lds > _MM_LDS_BUDGET:
                             continue
                         per_simd = 4 if (tpc <= 3 or nq > 1) else 2                               # waves per SIMD the instance's registers allow
@@ -1635,15 +1668,18 @@ def _mm_build(mode, S, pad, CI, CO, K, isz, osz, widx, force=None):
         return None
     _, PD, LD, cc, tpc, dbuf, PHB, W = max(cands, key=lambda c: (round(c[0], 9), c[3], -c[5]))
     tpc = {1: (3 if tpc <= 3 else tpc if tpc <= 6 else 8), 4: 4}[nq]
-    return MmPlan(CI=CI, CO=CO, ID=ID, IH=IH, IW=IW, OD=OD, OH=OH, OW=OW, nq=nq, ks=ks, PDT=PDT, PH=PH, PW=PW, PD=PD, sdi=sdi, shi=shi,
+    return MmPlan(CI=CI, CO=CO, co_blk=CO_l, ID=ID, IH=IH, IW=IW, OD=OD, OH=OH, OW=OW, nq=nq, ks=ks, PDT=PDT, PH=PH, PW=PW, PD=PD, sdi=sdi, shi=shi,
                   swi=swi, d0=d0, LD=LD, cc=cc, sdo=sdo, sho=sho, swo=swo, od0=od0, oh0=oh0, ow0=ow0, tpc=tpc, slack=slack, dbuf=dbuf,
                   PHB=PHB, hlo=hlo, hhi=hhi, waves=W,
                   tau=tau.reshape(-1), dlt=dlt.reshape(-1), aidx=aidx, mode=mode)
 
 
-def conv_mm(x, plan: MmPlan, aimg, bias, relu_in, scale, shift, per_group, mask_src=None, next_bn=None, relu_out=False):
+def conv_mm(x, plan: MmPlan, aimg, bias, relu_in, scale, shift, per_group, mask_src=None, next_bn=None, relu_out=False, stats_like=None):
     """One vg_conv_mm launch: x [N][CI][...] -> y [N][CO][OD][OH][OW] (pre-activation; rectified with relu_out); with next_bn also
-    the statistics partials."""
+    the statistics partials.  stats_like = the ConvSpec of a stride-2 transposed conv: the partials are then taken from y by
+    vg_tconv3d_s2_stats_of, in the layout and summation order of the register-tiled engine's fused launch, instead of in the
+    epilogue: y is the same bit for bit on either engine, the epilogue's own partials are not (a lane sums other elements), and with
+    this the consuming batch norm -- and so the step -- computes exactly what it computes on the register-tiled kernel."""
     lib = _lib.get_lib()
     N = x.shape[0]
     assert tuple(x.shape[1:]) == (plan.CI, plan.ID, plan.IH, plan.IW), (tuple(x.shape), plan.CI, plan.ID, plan.IH, plan.IW)
@@ -1651,6 +1687,14 @@ def conv_mm(x, plan: MmPlan, aimg, bias, relu_in, scale, shift, per_group, mask_
     d = plan.desc(N, relu_in, per_group if scale is not None else 1, relu_out)
     y = torch.empty((N, plan.CO, plan.OD, plan.OH, plan.OW), dtype=torch.float32, device=x.device)
     _chk(x); _chk(aimg)
+    if next_bn and stats_like is not None:
+        _call(x, 'vg_conv_mm', ctypes.byref(d), _p(x), _p(aimg), _p(tau), _p(dlt), _p(bias), _p(scale), _p(shift), _p(mask_src), _p(y), 1, 0, None)
+        _, cd, osz = conv_fwd_desc(stats_like, N, (plan.ID, plan.IH, plan.IW), relu_in, per_group if scale is not None else 1, relu_out)
+        assert tuple(osz) == (plan.OD, plan.OH, plan.OW) and stats_like.co == plan.CO
+        chunks = lib.size('vg_tconv3d_s2_stats_chunks', ctypes.byref(cd), int(next_bn))
+        part = torch.empty((N // int(next_bn)) * plan.CO * chunks * 2, dtype=torch.float64, device=x.device)
+        _call(x, 'vg_tconv3d_s2_stats_of', ctypes.byref(cd), _p(y), int(next_bn), 1, _p(part))
+        return y, part
     if next_bn:
         chunks = lib.size('vg_conv_mm_stats_chunks', ctypes.byref(d), int(next_bn))
         G = N // int(next_bn)
