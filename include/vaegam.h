@@ -509,6 +509,16 @@ int vg_gp_gain_fwd_tiled(const vg_gain_desc* d, const int64_t* table, const floa
 int vg_gp_gain_bwd_tiled(const vg_gain_desc* d, const int64_t* table, const float* params, const float* xu,
                          const float* covariates, int64_t ld_cov, const float* eps_beta, const double* hrf_taps, void* ws,
                          const float* g_task_var, const float* g_gp_kl, float* flat_grads, void* stream);
+/* What vg_gp_gain_fwd / _bwd (forced_tiled != 0: the _tiled pair) launch for this descriptor, from the launchers' own planner: host
+ * only, nothing is launched, no memory is touched.  out[0 .. VG_GAIN_PLAN_LEN):
+ *   path (0 = one workgroup with the B x B matrix in LDS, 1 = blocked, 2 = tiled), threads per workgroup of the factorisation and
+ *   solve kernels, panel width / panels / width of the last panel of the Cholesky, slab width / slabs per covariate / width of the
+ *   last slab of the backward solves, the largest dynamic LDS request in bytes of the forward and of the backward launches, the
+ *   number of launches of the forward and of the backward call.  (Path 0 is unblocked: one panel and one slab of width B.)
+ * n_out < VG_GAIN_PLAN_LEN (or out NULL) returns VG_ERR_ARG; a descriptor the launchers refuse returns their status and leaves their
+ * text in vg_last_error(). */
+#define VG_GAIN_PLAN_LEN 12
+int vg_gp_gain_plan(const vg_gain_desc* d, int32_t forced_tiled, int32_t* out, int32_t n_out);
 
 /* fused Adam (torch.optim.Adam defaults, vae_reg_GP.py:179,429) over one flat buffer:
  * p,g,m,v: n elements of fp32 (is_f64 = 0) or fp64 (is_f64 = 1).  step_size = lr/(1-b1^t),

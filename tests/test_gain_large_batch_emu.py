@@ -9,6 +9,7 @@ import torch
 import vae_gam_amd  # noqa: F401
 from vae_gam_amd import ops
 import kernel_cases as K
+import gain_cases as G
 
 
 @pytest.fixture(scope='module', autouse=True)
@@ -25,32 +26,14 @@ def test_tiled_gain_block_matches_float64_oracle(monkeypatch, B, n, jitter):
     K.run_gain_case('cpu', B=B, n=n, jitter=jitter, seed=B)
 
 
-def _gain_run(B, n=6, seed=3, kinds=('lin_hrf', 'gp', 'gp', 'gp_hrf', 'lin')):
-    """One forward + backward of ops.GpGain on the inputs run_gain_case builds; -> dict of float64 ndarrays."""
-    g = torch.Generator().manual_seed(seed)
-    P, table, xus = [], [], []
-
-    def put(t):
-        off = sum(x.numel() for x in P); P.append(t.reshape(-1).float()); return off
-    for kind in kinds:
-        row = [int(kind.startswith('gp')), int(kind.endswith('hrf')), len(xus), put(1 + torch.randn(1, 1, generator=g)),
-               put(0.3 * torch.randn(1, 1, generator=g)), 0, 0, 0, 0, 0]
-        if kind.startswith('gp'):
-            r = 0.2 * torch.randn(n, n, generator=g)
-            row[5], row[6] = put(torch.randn(1, n, generator=g)), put(2 * torch.eye(n) + r @ r.t())
-            row[7], row[8] = put(0.3 * torch.randn((), generator=g)), put(0.3 * torch.randn((), generator=g))
-            xus.append(torch.linspace(-4.1, 6.2, n))
-        table.append(row)
-    C = len(kinds)
-    flat = torch.cat(P)
-    cov = torch.randn(B, C + 2, generator=g) * 1.5
-    eps = torch.randn(C, B, generator=g)
-    wt = torch.randn(C, B, generator=g)
-    consts = ops.GainConsts(torch.tensor(table, dtype=torch.int64), torch.stack(xus).float(), K._hrf_taps(), n)
-    fp = flat.clone().requires_grad_(True)
+def _gain_run(B, n=6, seed=3, kinds=G.DEFAULT_KINDS):
+    """One forward + backward of ops.GpGain on the shared builder's inputs (tests/gain_cases.py); -> dict of float64 ndarrays."""
+    inp = G.build_inputs(B, n, seed, kinds)
+    consts = G.consts_of(inp, 'cpu')
+    fp = inp.flat.clone().requires_grad_(True)
     fg = torch.zeros_like(fp)
-    tv, kl, bm, bc, fb, sg, klt = ops.GpGain.apply(cov, eps, consts, fp.detach(), fg, None, fp)
-    ((tv * wt).sum() + 0.7 * kl.sum()).backward()
+    tv, kl, bm, bc, fb, sg, klt = ops.GpGain.apply(inp.cov, inp.eps, consts, fp.detach(), fg, None, fp)
+    ((tv * inp.wt).sum() + 0.7 * kl.sum()).backward()
     return {'task_var': tv.detach().double().numpy(), 'gp_kl': kl.detach().double().numpy(), 'beta_cov': bc.numpy(),
             'f_bar': fb.numpy(), 'Sigma': sg.numpy(), 'grads': fg.double().numpy()}
 

@@ -12,6 +12,7 @@ import vae_gam_amd  # noqa: F401
 from vae_gam_amd import _lib, ops
 from vae_gam_amd.vae_reg_GP import VAE
 import kernel_cases as K
+import gain_cases as G
 
 pytestmark = pytest.mark.gpu
 
@@ -24,23 +25,7 @@ def hip_lib():
     yield
 
 
-def _posterior_fp32_distances(xu, k_var, ls, qu_m, qu_S, xq, jitter=0.0):
-    """oracle.gp_posterior with the inducing-to-query distances rounded to fp32, as the reference's fp32 Knu (gp.py:90) and the
-    kernel (jitter 0) form them.  The plain oracle keeps them in float64: ~1e-7 relative on a distance, times cond(Ku), moves Sigma by
-    up to ~1e-5, and the factor of the near-singular B x B gain covariance (+1e-5 I) amplifies that with the batch.  Above B = 1000
-    it reached past run_gain_case's gain band (2e-6 of the largest gain): 1 of 5,125 gains at B = 1025 (3.3e-6), more at 2048 and in
-    the model at 1040 -- while every case with float64 distances (jitter > 0) stayed inside it."""
-    import vaegam_oracle as O
-    n = xu.shape[0]
-    step = (xu[1] - xu[0]).detach()
-    d0 = (xu[0].detach().double() - xq.detach().double())
-    knu_d = (d0.unsqueeze(0) + torch.arange(n, dtype=torch.float64).unsqueeze(1) * step.double()).float().to(xq.dtype)
-    knu = O.gp_kernel(knu_d, k_var, ls)
-    knn = O.gp_kernel(xq.unsqueeze(0) - xq.unsqueeze(1), k_var, ls)
-    idx = torch.arange(n, dtype=xq.dtype)
-    ku = O.gp_kernel((idx.unsqueeze(0) - idx.unsqueeze(1)).abs(), k_var, ls, step)
-    A = knu.T @ torch.inverse(ku)
-    return A @ torch.squeeze(qu_m), knn + (A @ (qu_S - ku) @ A.T)
+_posterior_fp32_distances = G.posterior_fp32_distances        # the jitter-0 reference of every gain test (tests/gain_cases.py)
 
 
 @pytest.mark.parametrize('B,n,jitter', [(1025, 6, 0.0), (1536, 6, 0.0), (2048, 6, 0.0), (2048, 64, 1e-4), (4096, 6, 0.0)])
@@ -51,25 +36,10 @@ def test_large_batch_gain_block_matches_float64_oracle(monkeypatch, B, n, jitter
     K.run_gain_case('cuda', B=B, n=n, jitter=jitter, seed=B)
 
 
-def _inputs(B, n=6, seed=3, kinds=('lin_hrf', 'gp', 'gp', 'gp_hrf', 'lin')):
-    g = torch.Generator().manual_seed(seed)
-    P, table, xus = [], [], []
-
-    def put(t):
-        off = sum(x.numel() for x in P); P.append(t.reshape(-1).float()); return off
-    for kind in kinds:
-        row = [int(kind.startswith('gp')), int(kind.endswith('hrf')), len(xus), put(1 + torch.randn(1, 1, generator=g)),
-               put(0.3 * torch.randn(1, 1, generator=g)), 0, 0, 0, 0, 0]
-        if kind.startswith('gp'):
-            r = 0.2 * torch.randn(n, n, generator=g)
-            row[5], row[6] = put(torch.randn(1, n, generator=g)), put(2 * torch.eye(n) + r @ r.t())
-            row[7], row[8] = put(0.3 * torch.randn((), generator=g)), put(0.3 * torch.randn((), generator=g))
-            xus.append(torch.linspace(-4.1, 6.2, n))
-        table.append(row)
-    C = len(kinds)
-    consts = ops.GainConsts(torch.tensor(table, dtype=torch.int64).cuda(), torch.stack(xus).float().cuda(), K._hrf_taps().cuda(), n)
-    return (consts, torch.cat(P).cuda(), (torch.randn(B, C + 2, generator=g) * 1.5).cuda(), torch.randn(C, B, generator=g).cuda(),
-            torch.randn(C, B, generator=g).cuda())
+def _inputs(B, n=6, seed=3, kinds=G.DEFAULT_KINDS):
+    """the shared builder's inputs on the GPU: (consts, flat parameters, covariates, eps, weights of the gains in the loss)"""
+    inp = G.build_inputs(B, n, seed, kinds)
+    return G.consts_of(inp, 'cuda'), inp.flat.cuda(), inp.cov.cuda(), inp.eps.cuda(), inp.wt.cuda()
 
 
 def _fwd_bwd(consts, flat, cov, eps, wt):
@@ -87,10 +57,7 @@ def test_batch_above_4096_is_refused():
         _fwd_bwd(consts, flat, cov, eps, wt)
 
 
-# |tiled - blocked| measured on the MI355X, relative to the largest |value|: 0 for task_var and 0 for the gradients at B = 256 and at
-# 1024 (the float64 results of the two blockings round to the same fp32 outputs).  3 x 0 would demand bit equality, which
-# the paths do not promise: the band is one fp32 ulp of the largest value instead
-TILED_VS_BLOCKED_BAND = {'task_var': 1.2e-7, 'grads': 1.2e-7}
+TILED_VS_BLOCKED_BAND = G.TILED_VS_BLOCKED_BAND
 
 
 @pytest.mark.parametrize('B', [256, 1024])

@@ -122,6 +122,7 @@ _PROTOS = {
     'vg_gp_gain_bwd': (ctypes.c_int, [ctypes.POINTER(GainDesc), vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp]),
     'vg_gp_gain_fwd_tiled': (ctypes.c_int, [ctypes.POINTER(GainDesc), vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     'vg_gp_gain_bwd_tiled': (ctypes.c_int, [ctypes.POINTER(GainDesc), vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp]),
+    'vg_gp_gain_plan': (ctypes.c_int, [ctypes.POINTER(GainDesc), i32, ctypes.POINTER(i32), i32]),
     'vg_adam_advance': (ctypes.c_int, [vp, f64, f64, f64, vp]),
     'vg_adam_step': (ctypes.c_int, [vp, vp, vp, vp, i64, i32, f64, f64, f64, vp, vp]),
     'vg_grad_guard_ws_bytes': (i64, [i64, i64]),
@@ -139,7 +140,10 @@ CONV_FAMILIES = ('direct', 'plane', 'tconv')                                    
 FC_PLAN_LEN = 36               # VG_FC_PLAN_LEN: 4 head values, then 8 per job (FC_PLAN_JOB_FIELDS) for up to 4 jobs
 FC_PLAN_HEAD_FIELDS = ('tile', 'grid', 'reduce_blocks', 'njobs')
 FC_PLAN_JOB_FIELDS = ('a_vec', 'b_vec', 'big', 'kchunk', 'gx', 'gy', 'first', 'blocks')
-GUARD_STATE_LEN = 8            # VG_GUARD_STATE_LEN: [total_norm, scale, apply, seen, skipped, clipped, norm_sum, norm_max]
+GAIN_PLAN_FIELDS = ('path', 'threads', 'panel', 'npanels', 'last_panel', 'slab', 'nslabs', 'last_slab', 'lds_fwd', 'lds_bwd',
+                    'launches_fwd', 'launches_bwd')                                                          # VG_GAIN_PLAN_LEN, in order
+GAIN_PATHS = ('lds', 'blocked', 'tiled')                                                                    # values of field 0
+GUARD_STATE_LEN = 8           # VG_GUARD_STATE_LEN: [total_norm, scale, apply, seen, skipped, clipped, norm_sum, norm_max]
 EXPORTS = tuple(_PROTOS)
 
 

@@ -1188,11 +1188,52 @@ GainArgs mk_args(const vg_gain_desc* d, const int64_t* table, const float* param
     return a;
 }
 
-size_t lds_bytes(int B) { return (size_t)(GP_T + (size_t)B * B) * sizeof(double); }                       // B <= GP_LDS_MAXB
-size_t lds_bytes_big(int B) { return (size_t)(GP_TB + (size_t)B * GP_NBP) * sizeof(double); }             // reduction scratch + one factorisation panel
-size_t lds_bytes_trsm(int B) { return (size_t)B * (GP_NB + gp_slab_cols(B)) * sizeof(double); }
+// What one forward / backward call launches for a batch of B volumes: the path, the blocking of the factorisation and of the solves, and
+// the dynamic LDS of every launch.  gain_fwd / gain_bwd and their tiled twins take grids and LDS sizes from here and vg_gp_gain_plan
+// reports the same record, so the arithmetic is written down once.
+struct GainPlan {
+    int path;                              // 0: one workgroup, B x B matrix in LDS;  1: blocked (panel / slab in LDS);  2: tiled
+    int threads;                           // threads per workgroup of the factorisation / solve kernels
+    int panel, npanels, last_panel;        // columns per panel of the Cholesky, panels, columns of the last panel
+    int slab, nslabs, last_slab;           // right-hand sides per slab of a solve, slabs per covariate, width of the last slab
+    size_t lds_main;                       // paths 0, 1: gain_fwd_k / gain_bwd_k;  path 2: the prelude / final kernels (reduction scratch)
+    size_t lds_solve;                      // path 1: gain_trsm_k;  path 2: every two-tile kernel
+    size_t lds_diag, lds_p1, lds_rows;     // path 2 only: gain_potrf_diag_k, gain_bwd_p1_k, gain_bwd_rows_k
+    size_t lds_fwd, lds_bwd;               // the largest request of each pass
+    int launches_fwd, launches_bwd;
+};
 
-size_t lds_bytes_tile2() { return (size_t)2 * GT * GTP * sizeof(double); }                                 // two 64 x 64 tiles
+GainPlan gain_plan(int B, bool forced) {
+    GainPlan p = {};
+    auto mx = [](size_t a_, size_t b_) { return a_ > b_ ? a_ : b_; };
+    auto blocks = [](int B_, int w, int& nblk, int& last) { nblk = (B_ + w - 1) / w; last = B_ - (nblk - 1) * w; };
+    if (forced || B > GP_MAXB_BLOCKED) {
+        p.path = 2; p.threads = GP_TT; p.panel = GT; p.slab = GT;
+        p.lds_main = (size_t)GP_TB * sizeof(double);
+        p.lds_solve = (size_t)2 * GT * GTP * sizeof(double);                                     // two 64 x 64 tiles
+        p.lds_diag = (size_t)GT * GTP * sizeof(double);
+        p.lds_p1 = (size_t)(B + GP_TT) * sizeof(double);
+        p.lds_rows = p.lds_solve + GP_TT * sizeof(double);
+        blocks(B, p.panel, p.npanels, p.last_panel); blocks(B, p.slab, p.nslabs, p.last_slab);
+        p.lds_fwd = mx(p.lds_main, mx(p.lds_solve, p.lds_diag));
+        p.lds_bwd = mx(mx(p.lds_main, p.lds_p1), mx(p.lds_solve, p.lds_rows));
+        p.launches_fwd = 2 + p.npanels + 2 * (p.npanels - 1) + 3; p.launches_bwd = 6;
+    } else if (B <= GP_LDS_MAXB) {
+        p.path = 0; p.threads = GP_T; p.panel = B; p.slab = B;                                   // unblocked: the whole matrix at once
+        p.lds_main = (size_t)(GP_T + (size_t)B * B) * sizeof(double);                            // reduction scratch + the matrix
+        blocks(B, p.panel, p.npanels, p.last_panel); blocks(B, p.slab, p.nslabs, p.last_slab);
+        p.lds_fwd = p.lds_bwd = p.lds_main;
+        p.launches_fwd = 2; p.launches_bwd = 1;
+    } else {
+        p.path = 1; p.threads = GP_TB; p.panel = GP_NB; p.slab = gp_slab_cols(B);
+        p.lds_main = (size_t)(GP_TB + (size_t)B * GP_NBP) * sizeof(double);                      // reduction scratch + one factorisation panel
+        p.lds_solve = (size_t)B * (GP_NB + p.slab) * sizeof(double);                             // a block row of L + the slab
+        blocks(B, p.panel, p.npanels, p.last_panel); blocks(B, p.slab, p.nslabs, p.last_slab);
+        p.lds_fwd = p.lds_main; p.lds_bwd = mx(p.lds_main, p.lds_solve);
+        p.launches_fwd = 2; p.launches_bwd = 4;
+    }
+    return p;
+}
 
 // max_b: the largest batch the caller's path takes (GP_MAXB_BLOCKED for the blocked / LDS path, GP_MAXB for the tiled one)
 int check(const vg_gain_desc* d, const char* who) {
@@ -1208,17 +1249,18 @@ int check(const vg_gain_desc* d, const char* who) {
 
 int gain_fwd_tiled(const vg_gain_desc* d, const GainArgs& a, double* kl_part, float* task_var, float* gp_kl, double* bm, double* bc,
                    double* fb, double* sg, hipStream_t s) {
-    const int C = d->C, B = d->B, T = gt_tiles(B);
-    vg_launch(gain_pre_k, dim3(C), dim3(GP_TB), (size_t)GP_TB * sizeof(double), s, a, kl_part, bm, fb);
-    vg_launch(gain_cov_k, dim3(C * T * T), dim3(GP_TT), lds_bytes_tile2(), s, a, bc, sg);
+    const GainPlan pl = gain_plan(d->B, true);
+    const int C = d->C, T = pl.npanels;
+    vg_launch(gain_pre_k, dim3(C), dim3(GP_TB), pl.lds_main, s, a, kl_part, bm, fb);
+    vg_launch(gain_cov_k, dim3(C * T * T), dim3(GP_TT), pl.lds_solve, s, a, bc, sg);
     int rc = vg_check_launch("gp_gain_fwd (tiled: prelude, covariance)");
     if (rc) return rc;
     for (int p = 0; p < T; ++p) {
-        vg_launch(gain_potrf_diag_k, dim3(C), dim3(GP_TT), (size_t)GT * GTP * sizeof(double), s, a, p);
+        vg_launch(gain_potrf_diag_k, dim3(C), dim3(GP_TT), pl.lds_diag, s, a, p);
         if (p + 1 < T) {
             const int nt = T - 1 - p, per = max(nt * (nt + 1) / 2, T);
-            vg_launch(gain_potrf_panel_k, dim3(C * T), dim3(GP_TT), lds_bytes_tile2(), s, a, p);
-            vg_launch(gain_potrf_update_k, dim3(C * per), dim3(GP_TT), lds_bytes_tile2(), s, a, p, per);
+            vg_launch(gain_potrf_panel_k, dim3(C * T), dim3(GP_TT), pl.lds_solve, s, a, p);
+            vg_launch(gain_potrf_update_k, dim3(C * per), dim3(GP_TT), pl.lds_solve, s, a, p, per);
         }
     }
     rc = vg_check_launch("gp_gain_fwd (tiled: Cholesky)");
@@ -1230,13 +1272,14 @@ int gain_fwd_tiled(const vg_gain_desc* d, const GainArgs& a, double* kl_part, fl
 }
 
 int gain_bwd_tiled(const vg_gain_desc* d, const GainArgs& a, const float* g_tv, const float* g_kl, float* G32, hipStream_t s) {
-    const int C = d->C, B = d->B, T = gt_tiles(B);
-    vg_launch(gain_bwd_p1_k, dim3(C * T), dim3(GP_TT), (size_t)(B + GP_TT) * sizeof(double), s, a, g_tv);
-    vg_launch(gain_trsm_tiled_k, dim3(C * T), dim3(GP_TT), lds_bytes_tile2(), s, a, 0);     // X = L^-T Phi          (column slabs)
-    vg_launch(gain_trsm_tiled_k, dim3(C * T), dim3(GP_TT), lds_bytes_tile2(), s, a, 1);     // X L^-1 = (L^-T X^T)^T (row slabs, in place)
-    vg_launch(gain_sym_k, dim3(C * T * (T + 1) / 2), dim3(GP_TT), lds_bytes_tile2(), s, a);
-    vg_launch(gain_bwd_rows_k, dim3(C * T), dim3(GP_TT), lds_bytes_tile2() + GP_TT * sizeof(double), s, a);
-    vg_launch(gain_bwd_fin_k, dim3(C), dim3(GP_TB), (size_t)GP_TB * sizeof(double), s, a, g_kl, G32);
+    const GainPlan pl = gain_plan(d->B, true);
+    const int C = d->C, T = pl.nslabs;
+    vg_launch(gain_bwd_p1_k, dim3(C * T), dim3(GP_TT), pl.lds_p1, s, a, g_tv);
+    vg_launch(gain_trsm_tiled_k, dim3(C * T), dim3(GP_TT), pl.lds_solve, s, a, 0);          // X = L^-T Phi          (column slabs)
+    vg_launch(gain_trsm_tiled_k, dim3(C * T), dim3(GP_TT), pl.lds_solve, s, a, 1);          // X L^-1 = (L^-T X^T)^T (row slabs, in place)
+    vg_launch(gain_sym_k, dim3(C * T * (T + 1) / 2), dim3(GP_TT), pl.lds_solve, s, a);
+    vg_launch(gain_bwd_rows_k, dim3(C * T), dim3(GP_TT), pl.lds_rows, s, a);
+    vg_launch(gain_bwd_fin_k, dim3(C), dim3(GP_TB), pl.lds_main, s, a, g_kl, G32);
     return vg_check_launch("gp_gain_bwd (tiled)");
 }
 
@@ -1250,6 +1293,17 @@ extern "C" int64_t vg_gp_gain_ws_bytes(int32_t C, int32_t B, int32_t n) {
     }
     GpLayout w = gp_layout(B, n);
     return (int64_t)(w.total * C + C + 8) * (int64_t)sizeof(double);       // C slabs + the per-covariate KL terms
+}
+
+extern "C" int vg_gp_gain_plan(const vg_gain_desc* d, int32_t forced_tiled, int32_t* out, int32_t n_out) {
+    if (!out || n_out < VG_GAIN_PLAN_LEN) { vg_set_error("vg_gp_gain_plan: out must hold %d values", VG_GAIN_PLAN_LEN); return VG_ERR_ARG; }
+    const int rc = check(d, "vg_gp_gain_plan");
+    if (rc) return rc;
+    const GainPlan p = gain_plan(d->B, forced_tiled != 0);
+    const int32_t rec[VG_GAIN_PLAN_LEN] = {p.path, p.threads, p.panel, p.npanels, p.last_panel, p.slab, p.nslabs, p.last_slab,
+                                           (int32_t)p.lds_fwd, (int32_t)p.lds_bwd, p.launches_fwd, p.launches_bwd};
+    for (int i = 0; i < VG_GAIN_PLAN_LEN; ++i) out[i] = rec[i];
+    return VG_OK;
 }
 
 // forced = 1: the tiled path at any batch (vg_gp_gain_fwd_tiled); otherwise by batch size
@@ -1266,9 +1320,10 @@ static int gain_fwd(const vg_gain_desc* d, const int64_t* table, const float* pa
     double* wsd = (double*)ws;
     double* kl_part = wsd + (size_t)w.total * d->C;
     GainArgs a = mk_args(d, table, params, xu, covariates, ld_cov, eps_beta, hrf_taps, wsd);
-    if (forced || d->B > GP_MAXB_BLOCKED) return gain_fwd_tiled(d, a, kl_part, task_var, gp_kl, beta_mean, beta_cov, f_bar, Sigma, s);
-    if (d->B <= GP_LDS_MAXB) vg_launch(gain_fwd_k<GP_T>, dim3(d->C), dim3(GP_T), lds_bytes(d->B), s, a, task_var, kl_part, beta_mean, beta_cov, f_bar, Sigma);
-    else vg_launch(gain_fwd_k<GP_TB>, dim3(d->C), dim3(GP_TB), lds_bytes_big(d->B), s, a, task_var, kl_part, beta_mean, beta_cov, f_bar, Sigma);
+    const GainPlan pl = gain_plan(d->B, forced);
+    if (pl.path == 2) return gain_fwd_tiled(d, a, kl_part, task_var, gp_kl, beta_mean, beta_cov, f_bar, Sigma, s);
+    if (pl.path == 0) vg_launch(gain_fwd_k<GP_T>, dim3(d->C), dim3(pl.threads), pl.lds_main, s, a, task_var, kl_part, beta_mean, beta_cov, f_bar, Sigma);
+    else vg_launch(gain_fwd_k<GP_TB>, dim3(d->C), dim3(pl.threads), pl.lds_main, s, a, task_var, kl_part, beta_mean, beta_cov, f_bar, Sigma);
     rc = vg_check_launch("gp_gain_fwd");
     if (rc) return rc;
     vg_launch(gain_kl_sum_k, dim3(1), dim3(64), 0, s, (const double*)kl_part, (int)d->C, gp_kl);
@@ -1285,17 +1340,17 @@ static int gain_bwd(const vg_gain_desc* d, const int64_t* table, const float* pa
     }
     GainArgs a = mk_args(d, table, params, xu, covariates, ld_cov, eps_beta, hrf_taps, (double*)ws);
     hipStream_t s = (hipStream_t)stream;
-    if (forced || d->B > GP_MAXB_BLOCKED) return gain_bwd_tiled(d, a, g_task_var, g_gp_kl, flat_grads, s);
-    if (d->B <= GP_LDS_MAXB) {
-        vg_launch(gain_bwd_k<GP_T, 0>, dim3(d->C), dim3(GP_T), lds_bytes(d->B), s, a, g_task_var, g_gp_kl, flat_grads);
+    const GainPlan pl = gain_plan(d->B, forced);
+    if (pl.path == 2) return gain_bwd_tiled(d, a, g_task_var, g_gp_kl, flat_grads, s);
+    if (pl.path == 0) {
+        vg_launch(gain_bwd_k<GP_T, 0>, dim3(d->C), dim3(pl.threads), pl.lds_main, s, a, g_task_var, g_gp_kl, flat_grads);
         return vg_check_launch("gp_gain_bwd");
     }
-    // large batches: Phi -> L^-T Phi -> (.) L^-1 -> the rest; each solve as slabs of 16 right-hand sides, a workgroup each
-    vg_launch(gain_bwd_k<GP_TB, 1>, dim3(d->C), dim3(GP_TB), lds_bytes_big(d->B), s, a, g_task_var, g_gp_kl, flat_grads);
-    const int nsl = (d->B + gp_slab_cols(d->B) - 1) / gp_slab_cols(d->B);
-    vg_launch(gain_trsm_k, dim3(d->C * nsl), dim3(GP_TB), lds_bytes_trsm(d->B), s, a, 0);      // X = L^-T Phi          (column slabs)
-    vg_launch(gain_trsm_k, dim3(d->C * nsl), dim3(GP_TB), lds_bytes_trsm(d->B), s, a, 1);      // X L^-1 = (L^-T X^T)^T (row slabs, in place)
-    vg_launch(gain_bwd_k<GP_TB, 2>, dim3(d->C), dim3(GP_TB), lds_bytes_big(d->B), s, a, g_task_var, g_gp_kl, flat_grads);
+    // large batches: Phi -> L^-T Phi -> (.) L^-1 -> the rest; each solve as slabs of pl.slab right-hand sides, a workgroup each
+    vg_launch(gain_bwd_k<GP_TB, 1>, dim3(d->C), dim3(pl.threads), pl.lds_main, s, a, g_task_var, g_gp_kl, flat_grads);
+    vg_launch(gain_trsm_k, dim3(d->C * pl.nslabs), dim3(pl.threads), pl.lds_solve, s, a, 0);   // X = L^-T Phi          (column slabs)
+    vg_launch(gain_trsm_k, dim3(d->C * pl.nslabs), dim3(pl.threads), pl.lds_solve, s, a, 1);   // X L^-1 = (L^-T X^T)^T (row slabs, in place)
+    vg_launch(gain_bwd_k<GP_TB, 2>, dim3(d->C), dim3(pl.threads), pl.lds_main, s, a, g_task_var, g_gp_kl, flat_grads);
     return vg_check_launch("gp_gain_bwd (large batch)");
 }
 

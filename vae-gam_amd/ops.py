@@ -1270,6 +1270,18 @@ class GainConsts:
         return _lib.GainDesc(self.C, int(B), self.n, int(self.hrf.numel()), self.jitter_b, self.jitter_ku, self.prior_var)
 
 
+GainPlan = namedtuple('GainPlan', _lib.GAIN_PLAN_FIELDS)
+
+
+def gain_plan(consts, B, forced=False) -> GainPlan:
+    """What GpGain would launch for a minibatch of B volumes (forced: under GAIN_FORCE_TILED), from the launchers' own planner
+    (vg_gp_gain_plan): nothing is launched.  `path` is 'lds', 'blocked' or 'tiled'; B > GAIN_MAX_BATCH raises VgError."""
+    d = consts.desc(B)
+    rec = (ctypes.c_int32 * len(GainPlan._fields))()
+    _lib.get_lib().call('vg_gp_gain_plan', ctypes.byref(d), int(bool(forced)), rec, len(rec))
+    return GainPlan(_lib.GAIN_PATHS[rec[0]], *rec[1:])
+
+
 class GpGain(torch.autograd.Function):
     """(covariates (B, >=C) fp32, eps_beta (C, B) fp32) -> gains task_var (C, B) fp32, gp_kl (1,) fp32 and float64 copies of
     beta_mean (C,B), beta_cov (C,B,B), f_bar (C,B), Sigma (C,B,B), kl terms (C,) for exports / tests: vg_gp_gain_fwd, one
