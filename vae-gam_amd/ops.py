@@ -16,12 +16,13 @@ downstream, and a consumer without a batch norm then runs without any prologue.
 import ctypes
 from collections import namedtuple
 from dataclasses import dataclass
-from typing import Optional, Tuple
+from typing import Tuple
 
 import torch
 
 from . import _lib
 from ._lib import ConvDesc, WgradDesc
+from .conv_mm_plan import MmPlan, mm_plan     # the vg_conv_mm planner; what uses its plans (USE_MM, mm_wins, conv_mm) is below
 
 BN_EPS = 1e-5            # nn.BatchNorm3d default (vae_reg_GP.py:194-196)
 
@@ -66,9 +67,7 @@ def _call(t, fn, *args):
 # the two chains do overlap: 8.10 -> 7.85 ms/step at batch 64 / 8 covariates, 3.20 -> 3.03 at batch 32 / 3.  On.
 import os as _os
 SIDE_STREAM = bool(int(_os.environ.get('VG_SIDE_STREAM', '1')))
-FUSE_LAST_BN_BWD = bool(int(_os.environ.get('VG_FUSE_LAST_BN_BWD', '1')))     # bnt5 backward + convt5 data gradient in two fused passes
-WGRAD_BN_SUMS = bool(int(_os.environ.get('VG_WGRAD_BN_SUMS', '1')))          # bnt5's backward reductions from convt5's grouped weight gradient (no reduce pass)
-FC_SIDE_STREAM = bool(int(_os.environ.get('VG_FC_SIDE_STREAM', '0')))     # fully connected dW/db on the second stream: measured 4.41 vs 4.28 ms/step (worse), off
+# (The fully connected dW/db on the second stream measured 4.41 vs 4.28 ms/step, worse: they stay on the main stream.)
 _SIDE = {}
 
 
@@ -143,6 +142,15 @@ def _chk(t, dtype=torch.float32):
     assert t.is_contiguous(), 'tensor must be contiguous'
     assert t.dtype == dtype, 'expected %s, got %s' % (dtype, t.dtype)
     return t
+
+
+def _out_or_new(out, shape, like):
+    """The `out=` convention of the parameter-gradient launches -> (tensor the launch writes, its accumulate flag): `out` (a
+    parameter's .grad, a view of the flat gradient buffer) is added into; without one a fresh fp32 tensor is written."""
+    if out is None:
+        return torch.empty(shape, dtype=torch.float32, device=like.device), 0
+    assert out.shape == shape and out.is_contiguous() and out.dtype == torch.float32
+    return out, 1
 
 
 # --------------------------------------------------------------------------- layer geometry
@@ -363,13 +371,9 @@ def conv_weight_grad(x, dy, spec: ConvSpec, relu_in=False, scale=None, shift=Non
     a, b = (x, dy) if a_is_x else (dy, x)
     nbytes = lib.size('vg_wgrad3d_ws_bytes', ctypes.byref(d))
     ws = torch.empty(max(nbytes // 4, 1), dtype=torch.float32, device=x.device)
-    if out is not None:          # accumulate straight into the parameter's .grad (a view of the flat gradient buffer)
-        assert out.shape == shape and out.is_contiguous() and out.dtype == torch.float32
-        _call(x, 'vg_wgrad3d', ctypes.byref(d), _p(a), _p(b), _p(scale), _p(shift), _p(ws), _p(out), 1)
-        return None
-    dw = torch.empty(shape, dtype=torch.float32, device=x.device)
-    _call(x, 'vg_wgrad3d', ctypes.byref(d), _p(a), _p(b), _p(scale), _p(shift), _p(ws), _p(dw), 0)
-    return dw
+    dw, acc = _out_or_new(out, shape, x)
+    _call(x, 'vg_wgrad3d', ctypes.byref(d), _p(a), _p(b), _p(scale), _p(shift), _p(ws), _p(dw), acc)
+    return None if acc else dw
 
 
 # --------------------------------------------------------------------------- batch norm pieces
@@ -391,39 +395,27 @@ def bn_stats(x, gamma, beta, relu, per_group, sync=None, pre=None):
     `sync(t)` (optional) all-reduces the raw [sum, sumsq, count] triples across data-parallel ranks.
     `pre`: the partials of relu(x) with THIS per_group that the kernel which wrote x accumulated
     (conv_forward(..., next_bn=per_group)); x is then not read at all."""
-    lib = _lib.get_lib()
     N, C = x.shape[0], x.shape[1]
     P = x[0, 0].numel()
     G = N // per_group
     out = torch.empty((4, G * C), dtype=torch.float32, device=x.device)
+    outs = (_p(out[0]), _p(out[1]), _p(out[2]), _p(out[3]))
+    # the producer launch writes the outputs itself -- or, data parallel, only the raw sums, which are all-reduced and then finalised
+    wr = outs if sync is None else (None,) * 4
     if pre is not None:
         assert relu, 'producer-side partials are statistics of relu(x)'
-        part = pre
-        assert part.dtype == torch.float64 and part.device == x.device and part.numel() % (G * C * 2) == 0
-        chunks = part.numel() // (G * C * 2)
-        sums = torch.empty((G * C, 3), dtype=torch.float64, device=x.device)
-        count = float(per_group * P)
-        if sync is None:
-            _call(x, 'vg_bn_stats_from_parts', _p(part), G, C, chunks, count, _p(gamma), _p(beta), BN_EPS, None, _p(sums),
-                     _p(out[0]), _p(out[1]), _p(out[2]), _p(out[3]))
-        else:
-            _call(x, 'vg_bn_stats_from_parts', _p(part), G, C, chunks, count, _p(gamma), _p(beta), BN_EPS, _p(sums), None,
-                     None, None, None, None)
-            sums = sync(sums)
-            _call(x, 'vg_bn_finalize', _p(sums), G, C, _p(gamma), _p(beta), BN_EPS, _p(out[0]), _p(out[1]), _p(out[2]),
-                     _p(out[3]))
-        return out[0], out[1], out[2], out[3]
-    ws = _bn_ws(x, N, C, P, per_group)
-    if sync is None:
-        _call(x, 'vg_bn_stats', _p(_chk(x)), N, C, P, per_group, int(relu), _p(gamma), _p(beta), BN_EPS, _p(ws), None,
-                 _p(out[0]), _p(out[1]), _p(out[2]), _p(out[3]))
+        assert pre.dtype == torch.float64 and pre.device == x.device and pre.numel() % (G * C * 2) == 0
+        chunks = pre.numel() // (G * C * 2)
+        sums = torch.empty((G * C, 3), dtype=torch.float64, device=x.device)       # without sync: the launch's workspace
+        _call(x, 'vg_bn_stats_from_parts', _p(pre), G, C, chunks, float(per_group * P), _p(gamma), _p(beta), BN_EPS,
+              *((None, _p(sums)) if sync is None else (_p(sums), None)), *wr)
     else:
-        sums = torch.empty((G * C, 3), dtype=torch.float64, device=x.device)
-        _call(x, 'vg_bn_stats', _p(_chk(x)), N, C, P, per_group, int(relu), _p(gamma), _p(beta), BN_EPS, _p(ws), _p(sums),
-                 None, None, None, None)
+        ws = _bn_ws(x, N, C, P, per_group)
+        sums = None if sync is None else torch.empty((G * C, 3), dtype=torch.float64, device=x.device)
+        _call(x, 'vg_bn_stats', _p(_chk(x)), N, C, P, per_group, int(relu), _p(gamma), _p(beta), BN_EPS, _p(ws), _p(sums), *wr)
+    if sync is not None:
         sums = sync(sums)
-        _call(x, 'vg_bn_finalize', _p(sums), G, C, _p(gamma), _p(beta), BN_EPS, _p(out[0]), _p(out[1]), _p(out[2]),
-                 _p(out[3]))
+        _call(x, 'vg_bn_finalize', _p(sums), G, C, _p(gamma), _p(beta), BN_EPS, *outs)
     return out[0], out[1], out[2], out[3]
 
 
@@ -440,7 +432,6 @@ def bn_backward_(dxe, p, gamma, mean, rstd, relu, per_group, sync=None, beta=Non
     gamma.grad / beta.grad when both exist (one launch instead of autograd's two sums + two adds).
     producer_bias_grad [C] (optional): += the per-channel sum of the result, i.e. the bias gradient of the layer that
     produced p, from the values the apply pass already holds (that layer then skips its own channel-sum pass)."""
-    lib = _lib.get_lib()
     N, C = p.shape[0], p.shape[1]
     P = p[0, 0].numel()
     G = N // per_group
@@ -448,25 +439,35 @@ def bn_backward_(dxe, p, gamma, mean, rstd, relu, per_group, sync=None, beta=Non
     sums = torch.empty((G * C, 2), dtype=torch.float64, device=p.device)
     _call(p, 'vg_bn_bwd_reduce', _p(_chk(dxe)), _p(_chk(p)), N, C, P, per_group, int(relu), _p(mean), _p(rstd), _p(ws),
              _p(sums))
-    count = float(per_group * P)
-    local = None
+
+    def apply(sums, count):
+        parts = torch.empty((2, G, C), dtype=torch.float32, device=p.device)
+        _call(p, 'vg_bn_bwd_apply', _p(dxe), _p(p), N, C, P, per_group, int(relu), _p(gamma), _p(mean), _p(rstd), _p(sums),
+                 count, _p(parts[0]), _p(parts[1]), _p(ws), _p(producer_bias_grad), 1)
+    return _bn_backward_tail(p, sums, per_group, sync, gamma, beta, producer_bias_grad, apply)
+
+
+def _bn_backward_tail(p, sums, per_group, sync, gamma, beta, producer_bias_grad, apply):
+    """What bn_backward_ and bn_backward_tconv1 do with the sums of their reduce launch: all-reduce them (data parallel), run the
+    caller's apply(sums, count) launch, then vg_bn_param_grad -> (dgamma, dbeta) with the conventions of bn_backward_."""
+    N, C = p.shape[0], p.shape[1]
+    G = N // per_group
+    count = float(per_group * p[0, 0].numel())
+    local = sums
     if sync is not None:
         local = sums.clone()                       # this rank's share of dgamma / dbeta (the gradient all-reduce sums them)
         sums = sync(sums)
         count = count * sync.world_size
-    parts = torch.empty((2, G, C), dtype=torch.float32, device=p.device)
     if producer_bias_grad is not None:
         assert producer_bias_grad.shape == (C,) and producer_bias_grad.is_contiguous() and producer_bias_grad.dtype == torch.float32
-    _call(p, 'vg_bn_bwd_apply', _p(dxe), _p(p), N, C, P, per_group, int(relu), _p(gamma), _p(mean), _p(rstd), _p(sums),
-             count, _p(parts[0]), _p(parts[1]), _p(ws), _p(producer_bias_grad), 1)
-    src = local if local is not None else sums      # data parallel: this rank's share (the gradient all-reduce sums them)
+    apply(sums, count)
     gg, bg = _grad_buf(gamma), _grad_buf(beta)
-    if gg is not None and bg is not None:
-        _call(p, 'vg_bn_param_grad', _p(src), G, C, _p(gg), _p(bg), 1)
-        return None, None
-    dg = torch.empty(C, dtype=torch.float32, device=p.device); db = torch.empty_like(dg)
-    _call(p, 'vg_bn_param_grad', _p(src), G, C, _p(dg), _p(db), 0)
-    return dg, db
+    if gg is None or bg is None:                   # straight into the .grad views only when both exist
+        gg = bg = None
+    dg, acc = _out_or_new(gg, (C,), p)
+    db, _ = _out_or_new(bg, (C,), p)
+    _call(p, 'vg_bn_param_grad', _p(local), G, C, _p(dg), _p(db), acc)
+    return (None, None) if acc else (dg, db)
 
 
 _GROUPED_OK = {}
@@ -525,7 +526,6 @@ def bn_backward_tconv1(dy, weight, p, gamma, mean, rstd, relu, per_group, sync=N
     _chk(dy); _chk(p)
     w = _chk(weight.detach().contiguous())
     G = N // per_group
-    P = ID * IH * IW
     ws = torch.empty(lib.size('vg_bn_tconv1_ws_bytes', N, C, ID, per_group) // 8, dtype=torch.float64, device=p.device)
     if dw_out is not None:
         assert dw_out.shape == weight.shape and dw_out.is_contiguous() and dw_out.dtype == torch.float32 and beta is not None
@@ -534,39 +534,22 @@ def bn_backward_tconv1(dy, weight, p, gamma, mean, rstd, relu, per_group, sync=N
     else:
         sums = torch.empty((G * C, 2), dtype=torch.float64, device=p.device)
         _call(p, 'vg_bn_bwd_reduce_tconv1', _p(dy), _p(w), _p(p), N, C, ID, IH, IW, per_group, int(relu), _p(mean), _p(rstd), _p(ws), _p(sums))
-    count = float(per_group * P)
-    local = None
-    if sync is not None:
-        local = sums.clone()
-        sums = sync(sums)
-        count = count * sync.world_size
     dp = torch.empty_like(p)
-    if producer_bias_grad is not None:
-        assert producer_bias_grad.shape == (C,) and producer_bias_grad.is_contiguous() and producer_bias_grad.dtype == torch.float32
-    _call(p, 'vg_bn_bwd_apply_tconv1', _p(dy), _p(w), _p(p), _p(dp), N, C, ID, IH, IW, per_group, int(relu), _p(gamma), _p(mean), _p(rstd),
-          _p(sums), count, _p(ws), _p(producer_bias_grad), 1)
-    src = local if local is not None else sums
-    gg, bg = _grad_buf(gamma), _grad_buf(beta)
-    if gg is not None and bg is not None:
-        _call(p, 'vg_bn_param_grad', _p(src), G, C, _p(gg), _p(bg), 1)
-        return dp, None, None
-    dg = torch.empty(C, dtype=torch.float32, device=p.device); db = torch.empty_like(dg)
-    _call(p, 'vg_bn_param_grad', _p(src), G, C, _p(dg), _p(db), 0)
-    return dp, dg, db
+
+    def apply(sums, count):
+        _call(p, 'vg_bn_bwd_apply_tconv1', _p(dy), _p(w), _p(p), _p(dp), N, C, ID, IH, IW, per_group, int(relu), _p(gamma), _p(mean), _p(rstd),
+              _p(sums), count, _p(ws), _p(producer_bias_grad), 1)
+    return (dp,) + _bn_backward_tail(p, sums, per_group, sync, gamma, beta, producer_bias_grad, apply)
 
 
 def channel_sum(x, out=None):
-    lib = _lib.get_lib()
+    """Per-channel sum of x [N][C][...] -> [C]; added into `out` (a bias .grad) when given, and None is returned."""
     N, C = x.shape[0], x.shape[1]
     P = x[0, 0].numel()
     ws = _bn_ws(x, N, C, P, N)
-    if out is not None:          # accumulate into an existing buffer (a bias .grad)
-        assert out.shape == (C,) and out.is_contiguous() and out.dtype == torch.float32
-        _call(x, 'vg_channel_sum', _p(_chk(x)), N, C, P, _p(ws), _p(out), 1)
-        return None
-    out = torch.empty(C, dtype=torch.float32, device=x.device)
-    _call(x, 'vg_channel_sum', _p(_chk(x)), N, C, P, _p(ws), _p(out), 0)
-    return out
+    s, acc = _out_or_new(out, (C,), x)
+    _call(x, 'vg_channel_sum', _p(_chk(x)), N, C, P, _p(ws), _p(s), acc)
+    return None if acc else s
 
 
 # --------------------------------------------------------------------------- autograd nodes
@@ -632,101 +615,92 @@ class BnConvAct(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy, *_unused):
         with label(ctx.spec.name + '/bwd'):
-            return BnConvAct._backward(ctx, dy) + (None, None, None, None, None)
+            return BnConvAct._backward(ctx, dy) + (None,) * 12        # forward's arguments after beta
 
     @staticmethod
     def _backward(ctx, dy):
+        """-> (dp, dweight, dbias, dgamma, dbeta)"""
         p_in, weight, gamma, beta, scale, shift, mean, rstd = ctx.saved_tensors
         spec, relu_in, per_group = ctx.spec, ctx.relu_in, ctx.per_group
         dy = dy.contiguous()
         # parameter gradients go straight into the parameters' .grad views of the flat gradient buffer when those
         # exist (no separate accumulate kernels); autograd then gets None for them
-        wg = weight.grad if (isinstance(weight, torch.nn.Parameter) and weight.grad is not None and weight.grad.is_contiguous()) else None
-        bias_t = ctx.bias_ref
-        bg = bias_t.grad if (isinstance(bias_t, torch.nn.Parameter) and bias_t.grad is not None and bias_t.grad.is_contiguous()) else None
-        direct_db = bg is not None and not (ctx.input_is_data and ctx.has_bn)
-        overlap = direct_db and wg is not None and not ctx.input_is_data
-        skip_db = ctx.bias_grad_by_consumer            # the consuming layer's batch-norm backward already added it to bias.grad
-        # last decoder stage (one output channel, 3x3x3 stride-1 transposed conv behind a batch norm): batch-norm backward fused with
-        # the recomputed data gradient; with WGRAD_BN_SUMS its reductions AND dW come out of one grouped weight-gradient launch
-        fuse_last = FUSE_LAST_BN_BWD and ctx.has_bn and not ctx.input_is_data and spec.kind == 'convt' and spec.stride == 1 \
-            and spec.co == 1 and tuple(spec.k) == (3, 3, 3) and tuple(spec.pad) == (0, 0, 0) and spec.ci <= 16
-        dw_by_bn = fuse_last and WGRAD_BN_SUMS and _grouped_wgrad_ok(p_in.shape, per_group)
-        if dw_by_bn:
-            overlap = False
-        if overlap:
-            with on_side_stream(dy, dy, p_in, scale, shift, wg, bg):
-                if not skip_db:
-                    channel_sum(dy, out=bg)
-                conv_weight_grad(p_in, dy, spec, relu_in, scale, shift, per_group, out=wg)
-            db = dw = None
-        elif skip_db:
-            db = None
-        else:
-            db = channel_sum(dy, out=bg) if direct_db else channel_sum(dy)
-        dgamma = dbeta = dp = None
+        wg, bg = _grad_buf(weight), _grad_buf(ctx.bias_ref)
         if ctx.input_is_data:
-            if ctx.has_bn:
-                assert spec.kind == 'conv' and spec.pad == (0, 0, 0) and not relu_in
-                G = p_in.shape[0] // per_group
-                assert G == 1
-                # weight gradient against the NORMALISED input xhat = (x-mean)*rstd, then
-                #   dw = gamma*dw_hat + beta*db ;  dgamma = <w, dw_hat> ; dbeta = <sum_k w, db>
-                # (two small launches instead of 14 torch ones at the very end of the step: vg_data_bn_nshift, vg_data_bn_grads)
-                nshift = torch.empty_like(mean)
-                _call(mean, 'vg_data_bn_nshift', _p(_chk(mean)), _p(_chk(rstd)), mean.numel(), _p(nshift))
-                dw_hat = conv_weight_grad(p_in, dy, spec, False, rstd, nshift, per_group)
-                gg, gbt = _grad_buf(gamma), _grad_buf(beta)
-                acc = wg is not None and bg is not None and gg is not None and gbt is not None
-                taps = spec.k[0] * spec.k[1] * spec.k[2]
-                dw = wg if acc else torch.empty_like(weight)
-                dbo = bg if acc else torch.empty_like(db)
-                dgamma = gg if acc else torch.empty_like(gamma)
-                dbeta = gbt if acc else torch.empty_like(beta)
-                _call(dy, 'vg_data_bn_grads', _p(_chk(dw_hat)), _p(_chk(db)), _p(_chk(weight)), _p(_chk(gamma)), _p(_chk(beta)),
-                      spec.co, spec.ci, taps, _p(dw), _p(dbo), _p(dgamma), _p(dbeta), int(acc))
-                if acc:
-                    return None, None, None, None, None, None, None, None, None, None, None, None
-                db = dbo
-            else:
-                dw = conv_weight_grad(p_in, dy, spec, relu_in, None, None, per_group, out=wg)
-            return None, dw, db, dgamma, dbeta, None, None, None, None, None, None, None
-        if dw_by_bn:
-            dw = None
-        elif not overlap:
-            dw = conv_weight_grad(p_in, dy, spec, relu_in, scale, shift, per_group, out=wg)
+            return (None,) + _data_layer_param_grads(ctx, dy, p_in, weight, gamma, beta, mean, rstd, wg, bg)
+        # last decoder stage: batch-norm backward fused with the recomputed data gradient (two passes); where the grouped weight
+        # gradient has an instance its reductions AND dW come out of that one launch (one pass)
+        fuse_last = ctx.has_bn and fuse_last_bn_bwd(spec)
+        dw_by_bn = fuse_last and _grouped_wgrad_ok(p_in.shape, per_group)
+        dw = db = dgamma = dbeta = None
+        # the bias sum (unless the consuming layer's batch-norm backward already added it to bias.grad) and the weight gradient: on
+        # the side stream when both go straight into .grad
+        overlap = wg is not None and bg is not None and not dw_by_bn
+        with on_side_stream(dy, dy, p_in, scale, shift, wg, bg, enabled=SIDE_STREAM and overlap):
+            if not ctx.bias_grad_by_consumer:
+                db = channel_sum(dy, out=bg)
+            if not dw_by_bn:
+                dw = conv_weight_grad(p_in, dy, spec, relu_in, scale, shift, per_group, out=wg)
         in_size = tuple(p_in.shape[2:])
         mmb = _mm_for(ctx.packed, weight, spec, 'bwd', tuple(dy.shape[2:]), in_size)
         wb = None
         if mmb is None:
             wb = ctx.packed.get(spec.name, 'bwd') if ctx.packed is not None else pack_weight(weight, spec, 'bwd')
-        if ctx.has_bn:
-            pbg = None
-            if ctx.producer_bias is not None:
-                pb = ctx.producer_bias
-                if pb.grad is None:
-                    # allocating here would leave the gradient OUTSIDE the flat buffer the optimiser and the all-reduce read
-                    raise RuntimeError('bn_conv_act: producer_bias.grad is not bound -- the consumer adds the producer\'s bias gradient into it '
-                                       '(FusedAdam binds every .grad to its flat buffer; a free-standing caller sets .grad = zeros first)')
-                pbg = pb.grad
-            if fuse_last:
-                # the data gradient is recomputed inside the batch-norm backward pass(es), never stored
-                dw_t = (wg if wg is not None else torch.zeros_like(weight)) if dw_by_bn else None
-                dp, dgamma, dbeta = bn_backward_tconv1(dy, weight, p_in, gamma, mean, rstd, relu_in, per_group, ctx.sync, beta, pbg, dw_out=dw_t)
-                if dw_by_bn and wg is None:
-                    dw = dw_t
-            else:
-                dp = conv_mm(dy, mmb[0], mmb[1], None, False, None, None, 1, None) if mmb is not None else \
-                    conv_backward_data(dy, wb, spec, in_size, None)
-                dgamma, dbeta = bn_backward_(dp, p_in, gamma, mean, rstd, relu_in, per_group, ctx.sync, beta, pbg)
+
+        def data_grad(mask_src):
+            if mmb is not None:
+                return conv_mm(dy, mmb[0], mmb[1], None, False, None, None, 1, mask_src)
+            return conv_backward_data(dy, wb, spec, in_size, mask_src)
+        if not ctx.has_bn:
+            return data_grad(p_in if relu_in else None), dw, db, None, None
+        pbg = None
+        if ctx.producer_bias is not None:
+            pbg = ctx.producer_bias.grad
+            if pbg is None:
+                # allocating here would leave the gradient OUTSIDE the flat buffer the optimiser and the all-reduce read
+                raise RuntimeError('bn_conv_act: producer_bias.grad is not bound -- the consumer adds the producer\'s bias gradient into it '
+                                   '(FusedAdam binds every .grad to its flat buffer; a free-standing caller sets .grad = zeros first)')
+        if fuse_last:
+            # the data gradient is recomputed inside the batch-norm backward pass(es), never stored
+            if dw_by_bn and wg is None:
+                dw = torch.zeros_like(weight)
+            dp, dgamma, dbeta = bn_backward_tconv1(dy, weight, p_in, gamma, mean, rstd, relu_in, per_group, ctx.sync, beta, pbg,
+                                                   dw_out=(wg if wg is not None else dw) if dw_by_bn else None)
         else:
-            msk = p_in if relu_in else None
-            dp = conv_mm(dy, mmb[0], mmb[1], None, False, None, None, 1, msk) if mmb is not None else \
-                conv_backward_data(dy, wb, spec, in_size, msk)
-        return dp, dw, db, dgamma, dbeta, None, None, None, None, None, None, None
+            dp = data_grad(None)
+            dgamma, dbeta = bn_backward_(dp, p_in, gamma, mean, rstd, relu_in, per_group, ctx.sync, beta, pbg)
+        return dp, dw, db, dgamma, dbeta
 
 
-_MM_SKIP = set(filter(None, _os.environ.get('VG_MM_SKIP', '').split(',')))
+def fuse_last_bn_bwd(spec: ConvSpec):
+    """Whether a layer behind a batch norm takes bn_backward_tconv1 instead of data gradient + bn_backward_: the decoder's last
+    stage, a 3x3x3 stride-1 transposed conv without padding onto ONE output channel from at most 16."""
+    return spec.kind == 'convt' and spec.stride == 1 and spec.co == 1 and tuple(spec.k) == (3, 3, 3) and tuple(spec.pad) == (0, 0, 0) \
+        and spec.ci <= 16
+
+
+def _data_layer_param_grads(ctx, dy, p_in, weight, gamma, beta, mean, rstd, wg, bg):
+    """BnConvAct's backward for the first encoder layer (input_is_data): no data gradient -> (dweight, dbias, dgamma, dbeta)."""
+    spec, per_group = ctx.spec, ctx.per_group
+    if not ctx.has_bn:
+        db = None if ctx.bias_grad_by_consumer else channel_sum(dy, out=bg)
+        return conv_weight_grad(p_in, dy, spec, ctx.relu_in, None, None, per_group, out=wg), db, None, None
+    assert spec.kind == 'conv' and spec.pad == (0, 0, 0) and not ctx.relu_in and not ctx.bias_grad_by_consumer
+    assert p_in.shape[0] // per_group == 1                         # one batch-norm group
+    # weight gradient against the NORMALISED input xhat = (x-mean)*rstd, then
+    #   dw = gamma*dw_hat + beta*db ;  dgamma = <w, dw_hat> ; dbeta = <sum_k w, db>
+    # (two small launches instead of 14 torch ones at the very end of the step: vg_data_bn_nshift, vg_data_bn_grads)
+    db = channel_sum(dy)
+    nshift = torch.empty_like(mean)
+    _call(mean, 'vg_data_bn_nshift', _p(_chk(mean)), _p(_chk(rstd)), mean.numel(), _p(nshift))
+    dw_hat = conv_weight_grad(p_in, dy, spec, False, rstd, nshift, per_group)
+    grads = (wg, bg, _grad_buf(gamma), _grad_buf(beta))
+    acc = all(g is not None for g in grads)                        # straight into the four .grad views, or four fresh tensors
+    if not acc:
+        grads = tuple(torch.empty_like(t) for t in (weight, db, gamma, beta))
+    _call(dy, 'vg_data_bn_grads', _p(_chk(dw_hat)), _p(_chk(db)), _p(_chk(weight)), _p(_chk(gamma)), _p(_chk(beta)),
+          spec.co, spec.ci, spec.k[0] * spec.k[1] * spec.k[2], *(_p(g) for g in grads), int(acc))
+    return (None,) * 4 if acc else grads
 
 
 def _halves_win(plan):
@@ -755,8 +729,6 @@ def mm_wins(plan):
     LDS budget, a unit is 57 MFMAs per wave between barriers; conv2 / conv4 forward).
     The 16-channel stride-2 transposed convs (convt2 forward, conv4's data gradient), two channel halves: _halves_win."""
     if plan is None:
-        return False
-    if _MM_SKIP and 'k%d' % plan.ks[0] in _MM_SKIP and (plan.PDT + plan.PD - 1) // plan.PD > 1:     # tuning knob: VG_MM_SKIP=k7,k9 -> those go register-tiled
         return False
     if USE_MM >= 2:
         return True
@@ -809,30 +781,35 @@ def _chk_mask(mask, Vn, like):
     return mask
 
 
-def _gam_forward(ctx, logits, gain, x, eps, glm, logits_bias, nat=None, grid=None, mask=None):
-    """forward of GamElbo (nat is None: everything on one grid), GamElboEmbed and GamElboMasked (mask given; nat may equal grid)"""
-    lib = _lib.get_lib()
+def _gam_launch(kind, logits, gain, x, eps, glm, nat, grid, mask, mid, tail):
+    """One launch of the GAM/ELBO kernels, kind 'fwd' | 'bwd':
+        vg_gam_elbo_<kind>[_embed | _masked](logits, gain, x, eps, glm, [mask,] *mid, C, B, V | nat, grid, ws, *tail)
+    Everything on one grid (nat is None): the plain entry; logits on `grid`, data on `nat`: _embed; with a voxel mask: _masked (nat may
+    equal grid).  The tensors are contiguous and of the kernels' dtypes (the callers' _chk); shapes and the mask are checked here."""
     G, B, V = logits.shape
     C = G - 1
+    ws = torch.empty(_lib.get_lib().size('vg_gam_ws_bytes', C, B, V) // 4 + 1, dtype=torch.float32, device=x.device)
+    ins = [_p(logits), _p(gain), _p(x), _p(eps), _p(glm)]
+    if nat is None:
+        assert mask is None, 'a mask needs nat and grid (they may be equal)'
+        fn, dims = 'vg_gam_elbo_' + kind, (C, B, V)
+    else:
+        Vn = int(nat[0]) * int(nat[1]) * int(nat[2])
+        assert V == int(grid[0]) * int(grid[1]) * int(grid[2]) and x.shape == (B, Vn) and eps.shape == (Vn,) and (C == 0 or glm.shape == (C, Vn))
+        fn, dims = 'vg_gam_elbo_%s_%s' % (kind, 'embed' if mask is None else 'masked'), (C, B, _i3(nat), _i3(grid))
+        if mask is not None:
+            ins.append(_p(_chk_mask(mask, Vn, x)))
+    _call(x, fn, *ins, *mid, *dims, _p(ws), *tail)
+
+
+def _gam_forward(ctx, logits, gain, x, eps, glm, logits_bias, nat=None, grid=None, mask=None):
+    """forward of GamElbo (nat is None: everything on one grid), GamElboEmbed and GamElboMasked (mask given; nat may equal grid)"""
+    G, B, V = logits.shape
     logits = _chk(logits.contiguous()); gain = _chk(gain.contiguous()); x = _chk(x.contiguous())
     eps = _chk(eps.contiguous(), torch.float64); glm = _chk(glm.contiguous())
-    ws = torch.empty(lib.size('vg_gam_ws_bytes', C, B, V) // 4 + 1, dtype=torch.float32, device=x.device)
     slp = torch.empty(B, dtype=torch.float32, device=x.device)
-    dist = torch.empty((C, B), dtype=torch.float32, device=x.device)
-    if mask is not None:
-        Vn = nat[0] * nat[1] * nat[2]
-        assert V == grid[0] * grid[1] * grid[2] and x.shape == (B, Vn) and eps.shape == (Vn,) and (C == 0 or glm.shape == (C, Vn))
-        mask = _chk_mask(mask, Vn, x)
-        _call(x, 'vg_gam_elbo_fwd_masked', _p(logits), _p(gain), _p(x), _p(eps), _p(glm), _p(mask), C, B, _i3(nat), _i3(grid), _p(ws),
-                 _p(slp), _p(dist), None)
-    elif nat is None:
-        _call(x, 'vg_gam_elbo_fwd', _p(logits), _p(gain), _p(x), _p(eps), _p(glm), C, B, V, _p(ws), _p(slp), _p(dist),
-                 None)
-    else:
-        Vn = nat[0] * nat[1] * nat[2]
-        assert V == grid[0] * grid[1] * grid[2] and x.shape == (B, Vn) and eps.shape == (Vn,) and (C == 0 or glm.shape == (C, Vn))
-        _call(x, 'vg_gam_elbo_fwd_embed', _p(logits), _p(gain), _p(x), _p(eps), _p(glm), C, B, _i3(nat), _i3(grid), _p(ws), _p(slp),
-                 _p(dist), None)
+    dist = torch.empty((G - 1, B), dtype=torch.float32, device=x.device)
+    _gam_launch('fwd', logits, gain, x, eps, glm, nat, grid, mask, (), (_p(slp), _p(dist), None))
     ctx.save_for_backward(logits, gain, x, eps, glm, dist)
     ctx.logits_bias, ctx.nat, ctx.grid, ctx.mask = logits_bias, nat, grid, mask
     return slp, dist
@@ -840,7 +817,6 @@ def _gam_forward(ctx, logits, gain, x, eps, glm, logits_bias, nat=None, grid=Non
 
 def _gam_backward(ctx, g_slp, g_dist):
     """-> d_logits, d_gain, d_eps; sum(d_logits) is added into ctx.logits_bias.grad"""
-    lib = _lib.get_lib()
     logits, gain, x, eps, glm, dist = ctx.saved_tensors
     tot = None
     if ctx.logits_bias is not None:
@@ -849,22 +825,12 @@ def _gam_backward(ctx, g_slp, g_dist):
         if pb.grad is None:
             raise RuntimeError('GamElbo: logits_bias.grad is not bound (see bn_conv_act: the bias gradient is added into the caller\'s buffer)')
         tot = pb.grad
-    G, B, V = logits.shape
-    C = G - 1
     g_slp = _chk(g_slp.contiguous()); g_dist = _chk(g_dist.contiguous())
-    ws = torch.empty(lib.size('vg_gam_ws_bytes', C, B, V) // 4 + 1, dtype=torch.float32, device=x.device)
     d_logits = torch.empty_like(logits)
     d_gain = torch.empty_like(gain)
     d_eps = torch.empty_like(eps)
-    if ctx.mask is not None:
-        _call(x, 'vg_gam_elbo_bwd_masked', _p(logits), _p(gain), _p(x), _p(eps), _p(glm), _p(ctx.mask), _p(dist), _p(g_slp), _p(g_dist),
-                 C, B, _i3(ctx.nat), _i3(ctx.grid), _p(ws), _p(d_logits), _p(d_gain), _p(d_eps), _p(tot), 1)
-    elif ctx.nat is None:
-        _call(x, 'vg_gam_elbo_bwd', _p(logits), _p(gain), _p(x), _p(eps), _p(glm), _p(dist), _p(g_slp), _p(g_dist),
-                 C, B, V, _p(ws), _p(d_logits), _p(d_gain), _p(d_eps), _p(tot), 1)
-    else:
-        _call(x, 'vg_gam_elbo_bwd_embed', _p(logits), _p(gain), _p(x), _p(eps), _p(glm), _p(dist), _p(g_slp), _p(g_dist),
-                 C, B, _i3(ctx.nat), _i3(ctx.grid), _p(ws), _p(d_logits), _p(d_gain), _p(d_eps), _p(tot), 1)
+    _gam_launch('bwd', logits, gain, x, eps, glm, ctx.nat, ctx.grid, ctx.mask, (_p(dist), _p(g_slp), _p(g_dist)),
+                (_p(d_logits), _p(d_gain), _p(d_eps), _p(tot), 1))
     return d_logits, d_gain, d_eps
 
 
@@ -926,35 +892,46 @@ def embed_volumes(x, nat, grid):
     return out
 
 
+def _latent_forward(ctx, mu, w, a, eps_w, eps_d, G):
+    """vg_latent_fwd on mu, w, a [B, L] (contiguous fp32, each its own tensor or a slice of one) -> (zcat, kl, d, flag)"""
+    B, L = mu.shape
+    eps_w = _chk(eps_w.contiguous()); eps_d = _chk(eps_d.contiguous())
+    assert w.shape == (B, L) and a.shape == (B, L) and eps_d.shape == (B, L) and eps_w.numel() == B
+    zcat = torch.empty((G * B, L + G), dtype=torch.float32, device=mu.device)
+    kl = torch.empty(B, dtype=torch.float32, device=mu.device)
+    d = torch.empty((B, L), dtype=torch.float32, device=mu.device)
+    flag = torch.empty(1, dtype=torch.float32, device=mu.device)
+    _call(mu, 'vg_latent_fwd', _p(mu), _p(w), _p(a), _p(eps_w), _p(eps_d), B, L, G, _p(zcat), _p(kl), _p(d), _p(flag))
+    ctx.G = G
+    ctx.mark_non_differentiable(d)
+    return zcat, kl, d, flag, eps_w, eps_d
+
+
+def _latent_backward(ctx, mu, w, d, flag, eps_w, eps_d, g_zcat, g_kl, g_mu, g_w, g_a):
+    """vg_latent_bwd: the gradients are written into g_mu, g_w, g_a [B, L]"""
+    B, L = mu.shape
+    gz = _p(_chk(g_zcat.contiguous())) if g_zcat is not None else None
+    gk = _p(_chk(g_kl.contiguous())) if g_kl is not None else None
+    _call(mu, 'vg_latent_bwd', _p(mu), _p(w), _p(d), _p(flag), _p(eps_w), _p(eps_d), gz, gk, B, L, ctx.G,
+             _p(g_mu), _p(g_w), _p(g_a))
+
+
 class LatentSample(torch.autograd.Function):
     """(mu, w, a, eps_w, eps_d, G) -> (zcat[G*B, L+G], kl_z[B], d[B, L]); one launch each way
     (vae_reg_GP.py:321-329, 339-342, 400).  `a` is fc43's output (d = exp(a) + the batch-wide 1e-6 floor)."""
 
     @staticmethod
     def forward(ctx, mu, w, a, eps_w, eps_d, G):
-        B, L = mu.shape
         mu = _chk(mu.contiguous()); w = _chk(w.contiguous()); a = _chk(a.contiguous())
-        eps_w = _chk(eps_w.contiguous()); eps_d = _chk(eps_d.contiguous())
-        assert w.shape == (B, L) and a.shape == (B, L) and eps_d.shape == (B, L) and eps_w.numel() == B
-        zcat = torch.empty((G * B, L + G), dtype=torch.float32, device=mu.device)
-        kl = torch.empty(B, dtype=torch.float32, device=mu.device)
-        d = torch.empty((B, L), dtype=torch.float32, device=mu.device)
-        flag = torch.empty(1, dtype=torch.float32, device=mu.device)
-        _call(mu, 'vg_latent_fwd', _p(mu), _p(w), _p(a), _p(eps_w), _p(eps_d), B, L, G, _p(zcat), _p(kl), _p(d), _p(flag))
+        zcat, kl, d, flag, eps_w, eps_d = _latent_forward(ctx, mu, w, a, eps_w, eps_d, G)
         ctx.save_for_backward(mu, w, d, flag, eps_w, eps_d)
-        ctx.G = G
-        ctx.mark_non_differentiable(d)
         return zcat, kl, d
 
     @staticmethod
     def backward(ctx, g_zcat, g_kl, _g_d):
         mu, w, d, flag, eps_w, eps_d = ctx.saved_tensors
-        B, L = mu.shape
         g_mu = torch.empty_like(mu); g_w = torch.empty_like(mu); g_a = torch.empty_like(mu)
-        gz = _p(_chk(g_zcat.contiguous())) if g_zcat is not None else None
-        gk = _p(_chk(g_kl.contiguous())) if g_kl is not None else None
-        _call(mu, 'vg_latent_bwd', _p(mu), _p(w), _p(d), _p(flag), _p(eps_w), _p(eps_d), gz, gk, B, L, ctx.G,
-                 _p(g_mu), _p(g_w), _p(g_a))
+        _latent_backward(ctx, mu, w, d, flag, eps_w, eps_d, g_zcat, g_kl, g_mu, g_w, g_a)
         return g_mu, g_w, g_a, None, None, None
 
 
@@ -965,28 +942,15 @@ class LatentSampleStacked(torch.autograd.Function):
     @staticmethod
     def forward(ctx, mwa, eps_w, eps_d, G):
         mwa = _chk(mwa.contiguous())
-        _, B, L = mwa.shape
-        eps_w = _chk(eps_w.contiguous()); eps_d = _chk(eps_d.contiguous())
-        assert eps_d.shape == (B, L) and eps_w.numel() == B
-        zcat = torch.empty((G * B, L + G), dtype=torch.float32, device=mwa.device)
-        kl = torch.empty(B, dtype=torch.float32, device=mwa.device)
-        d = torch.empty((B, L), dtype=torch.float32, device=mwa.device)
-        flag = torch.empty(1, dtype=torch.float32, device=mwa.device)
-        _call(mwa, 'vg_latent_fwd', _p(mwa[0]), _p(mwa[1]), _p(mwa[2]), _p(eps_w), _p(eps_d), B, L, G, _p(zcat), _p(kl), _p(d), _p(flag))
+        zcat, kl, d, flag, eps_w, eps_d = _latent_forward(ctx, mwa[0], mwa[1], mwa[2], eps_w, eps_d, G)
         ctx.save_for_backward(mwa, d, flag, eps_w, eps_d)
-        ctx.G = G
-        ctx.mark_non_differentiable(d)
         return zcat, kl, d
 
     @staticmethod
     def backward(ctx, g_zcat, g_kl, _g_d):
         mwa, d, flag, eps_w, eps_d = ctx.saved_tensors
-        _, B, L = mwa.shape
         g = torch.empty_like(mwa)
-        gz = _p(_chk(g_zcat.contiguous())) if g_zcat is not None else None
-        gk = _p(_chk(g_kl.contiguous())) if g_kl is not None else None
-        _call(mwa, 'vg_latent_bwd', _p(mwa[0]), _p(mwa[1]), _p(d), _p(flag), _p(eps_w), _p(eps_d), gz, gk, B, L, ctx.G,
-                 _p(g[0]), _p(g[1]), _p(g[2]))
+        _latent_backward(ctx, mwa[0], mwa[1], d, flag, eps_w, eps_d, g_zcat, g_kl, g[0], g[1], g[2])
         return g, None, None, None
 
 
@@ -1151,16 +1115,6 @@ class HeadsAct(torch.autograd.Function):
         return gh, None, None, None, None, None, None, None, None
 
 
-_ONES = {}
-
-
-def _ones(n, device):
-    key = (n, str(device))
-    if key not in _ONES:
-        _ONES[key] = torch.ones(n, dtype=torch.float32, device=device)
-    return _ONES[key]
-
-
 def linear_act(layer, x, relu, relu_in=False):
     return LinearAct.apply(x, layer.weight, layer.bias, relu, relu_in)
 
@@ -1169,24 +1123,13 @@ def gam_maps(logits, gain, x, eps, glm, nat=None, grid=None, mask=None):
     """Reconstruction path (vae_reg_GP.py:331,391-392): the C+2 maps [base, cons_1..C, full_rec] as [C+2,B,V].
     With nat / grid (see GamElboEmbed) the logits are on the grid and the maps come out on the native grid: V = V_nat.
     With mask (see GamElboMasked; needs nat and grid, which may be equal) every map is exactly 0 outside the mask."""
-    lib = _lib.get_lib()
     G, B, V = logits.shape
-    C = G - 1
     Vn = V if nat is None else int(nat[0]) * int(nat[1]) * int(nat[2])
-    ws = torch.empty(lib.size('vg_gam_ws_bytes', C, B, V) // 4 + 1, dtype=torch.float32, device=x.device)
     slp = torch.empty(B, dtype=torch.float32, device=x.device)
-    dist = torch.empty((max(C, 1), B), dtype=torch.float32, device=x.device)
+    dist = torch.empty((max(G - 1, 1), B), dtype=torch.float32, device=x.device)
     maps = torch.empty((G + 1, B, Vn), dtype=torch.float32, device=x.device)
-    ptrs = (_p(_chk(logits.contiguous())), _p(_chk(gain.contiguous())), _p(_chk(x.contiguous())),
-            _p(_chk(eps.contiguous(), torch.float64)), _p(_chk(glm.contiguous())))
-    if mask is not None:
-        assert V == int(grid[0]) * int(grid[1]) * int(grid[2]) and x.shape == (B, Vn)
-        _call(x, 'vg_gam_elbo_fwd_masked', *ptrs, _p(_chk_mask(mask, Vn, x)), C, B, _i3(nat), _i3(grid), _p(ws), _p(slp), _p(dist), _p(maps))
-    elif nat is None:
-        _call(x, 'vg_gam_elbo_fwd', *ptrs, C, B, V, _p(ws), _p(slp), _p(dist), _p(maps))
-    else:
-        assert V == int(grid[0]) * int(grid[1]) * int(grid[2]) and x.shape == (B, Vn)
-        _call(x, 'vg_gam_elbo_fwd_embed', *ptrs, C, B, _i3(nat), _i3(grid), _p(ws), _p(slp), _p(dist), _p(maps))
+    _gam_launch('fwd', _chk(logits.contiguous()), _chk(gain.contiguous()), _chk(x.contiguous()), _chk(eps.contiguous(), torch.float64),
+                _chk(glm.contiguous()), nat, grid, mask, (), (_p(slp), _p(dist), _p(maps)))
     return maps
 
 
@@ -1366,13 +1309,16 @@ def adam_advance_(state, lr, b1, b2):
     _call(state, 'vg_adam_advance', _p(_chk(state, torch.float64)), float(lr), float(b1), float(b2))
 
 
-def adam_step_(p, g, m, v, b1, b2, eps, step_scalars):
-    """In-place fused Adam over one flat buffer (fp32 or fp64)."""
-    lib = _lib.get_lib()
+def _adam_step(fn, p, g, m, v, b1, b2, eps, step_scalars, *guard):
     assert p.dtype == g.dtype == m.dtype == v.dtype and p.dtype in (torch.float32, torch.float64)
     assert p.is_contiguous() and g.is_contiguous() and m.is_contiguous() and v.is_contiguous()
-    _call(p, 'vg_adam_step', _p(p), _p(g), _p(m), _p(v), p.numel(), int(p.dtype == torch.float64), float(b1), float(b2),
-             float(eps), _p(_chk(step_scalars, torch.float64)))
+    _call(p, fn, _p(p), _p(g), _p(m), _p(v), p.numel(), int(p.dtype == torch.float64), float(b1), float(b2),
+          float(eps), *(_p(_chk(t, torch.float64)) for t in (step_scalars,) + guard))
+
+
+def adam_step_(p, g, m, v, b1, b2, eps, step_scalars):
+    """In-place fused Adam over one flat buffer (fp32 or fp64)."""
+    _adam_step('vg_adam_step', p, g, m, v, b1, b2, eps, step_scalars)
 
 
 # --------------------------------------------------------------------------- gradient guard (opt-in; include/vaegam.h)
@@ -1408,10 +1354,7 @@ def adam_advance_guarded_(state, lr, b1, b2, guard):
 
 def adam_step_guarded_(p, g, m, v, b1, b2, eps, step_scalars, guard):
     """adam_step_ on g * scale; touches nothing when the guard's apply flag is 0.  g itself is left unscaled."""
-    assert p.dtype == g.dtype == m.dtype == v.dtype and p.dtype in (torch.float32, torch.float64)
-    assert p.is_contiguous() and g.is_contiguous() and m.is_contiguous() and v.is_contiguous()
-    _call(p, 'vg_adam_step_guarded', _p(p), _p(g), _p(m), _p(v), p.numel(), int(p.dtype == torch.float64), float(b1), float(b2),
-          float(eps), _p(_chk(step_scalars, torch.float64)), _p(_chk(guard, torch.float64)))
+    _adam_step('vg_adam_step_guarded', p, g, m, v, b1, b2, eps, step_scalars, guard)
 
 
 # --------------------------------------------------------------------------- device-resident input path (include/vaegam.h)
@@ -1431,259 +1374,8 @@ def volume_gather(arena, files, row_file, row_vol, idx, shape, dtype, divisor, o
     return out
 
 
-# --------------------------------------------------------------------------- matrix-core convolution plans (vg_conv_mm)
-USE_MM =int(_os.environ.get('VG_CONV_MM', '1'))            # 0: off; 1: where it measured faster (mm_wins); 2: wherever a plan exists
-_MM_LDS_BUDGET = 150 * 1024
-_MM_LDS_CU = 160 * 1024                                     # LDS of a CU: what co-resident blocks share
-# (mode, stride, CI, CO, kernel, read size, write size) -> (waves, PD, PHB, cc, dbuf): tools/diag/mm_sweep.py at batch 64, 8 covariates
-_MM_TUNED = {
-    ('corr', 1, 16, 16, (3, 3, 3), (6, 8, 5), (8, 10, 7)): (8, 4, 10, 16, 0),    # convt1 forward 66.7 us (score's choice: 78)
-    ('corr', 1, 16, 16, (3, 3, 3), (8, 10, 7), (6, 8, 5)): (8, 3, 8, 16, 0),     # convt1 data gradient 37.8
-    ('corr', 2, 16, 16, (3, 3, 3), (16, 21, 14), (8, 10, 7)): (8, 2, 10, 8, 0),   # convt2 data gradient 83.2
-    ('corr', 1, 16, 8, (3, 3, 3), (17, 21, 14), (19, 23, 16)): (8, 1, 23, 8, 0),  # conv3 data gradient 61.6
-    ('corr', 1, 8, 16, (3, 3, 3), (19, 23, 16), (17, 21, 14)): (8, 1, 21, 8, 0),  # conv3 forward 46 (score's choice, a 6-row slab: 51)
-    ('corr', 1, 8, 16, (3, 3, 3), (18, 23, 16), (16, 21, 14)): (8, 2, 11, 8, 1),  # convt3 data gradient 242 (whole planes: 254)
-    ('tconv', 2, 8, 8, (5, 3, 3), (18, 23, 16), (39, 47, 33)): (8, 2, 12, 8, 1),   # convt4 forward 610 (whole planes, single buffer: 656 in the same run)
-    # two channel halves (the score's choices; the runners-up of the sweep behind them)
-    ('tconv', 2, 16, 16, (3, 3, 3), (8, 10, 7), (16, 21, 14)): (8, 5, 11, 16, 0),  # convt2 forward 138-142 (3 planes, double-buffered: 158; 4-wave blocks of 2 planes: 166)
-    ('tconv', 2, 16, 16, (3, 3, 3), (18, 22, 15), (37, 45, 31)): (8, 1, 23, 16, 0),  # 82x98x70 convt2 forward 1619-1686 (4 planes x 8-row slabs: 1747; double-buffered: 1856)
-}
-_MM_WAVES = 8
-
-
-class MmPlan:
-    """Host-side description of one conv / transposed-conv launch for vg_conv_mm (include/vaegam.h): position grid, staging
-    geometry and the window-offset tables, plus `aidx` -- for every A-image slot the index of the weight it holds inside the
-    layer's own weight tensor (-1 = zero).  CO: channels of y; co_blk: channels a block computes (CO, or 8 of 16: two halves, whose
-    images sit back to back in `aidx`)."""
-
-    def __init__(self, **kw):
-        self.__dict__.update(kw)
-        self._dev = {}
-
-    def tables(self, device):
-        key = str(device)
-        if key not in self._dev:
-            self._dev[key] = (torch.from_numpy(self.tau).to(device), torch.from_numpy(self.dlt).to(device), torch.from_numpy(self.aidx).to(device))
-        return self._dev[key]
-
-    def desc(self, N, relu_in, per_group, relu_out=False):
-        d = _lib.MmDesc()
-        for k in ('CI', 'ID', 'IH', 'IW', 'OD', 'OH', 'OW', 'nq', 'PDT', 'PH', 'PW', 'PD', 'sdi', 'shi', 'swi', 'd0', 'LD', 'cc', 'sdo', 'sho',
-                  'swo', 'tpc', 'slack', 'dbuf', 'PHB', 'hlo', 'hhi', 'waves'):
-            setattr(d, k, int(getattr(self, k)))
-        d.N, d.relu_in, d.per_group, d.relu_out = int(N), int(bool(relu_in)), int(per_group), int(bool(relu_out))
-        d.CO, d.co_tot = int(self.co_blk), int(self.CO)                 # channels per block (the matrix rows' channels), channels of y
-        for q in range(4):
-            d.ks[q] = int(self.ks[q]) if q < self.nq else 0
-            d.od0[q] = int(self.od0[q]) if q < self.nq else 0
-            d.oh0[q] = int(self.oh0[q]) if q < self.nq else 0
-            d.ow0[q] = int(self.ow0[q]) if q < self.nq else 0
-        return d
-
-    def gather(self, weight):
-        """A image from a weight tensor (layer tests / un-packed path; the model gathers all layers in one launch)."""
-        _, _, aidx = self.tables(weight.device)
-        flat = weight.detach().reshape(-1)
-        a = flat[aidx.clamp_min(0).long()]
-        return torch.where(aidx >= 0, a, torch.zeros_like(a)).contiguous()
-
-
-def _mm_problem(spec: ConvSpec, direction: str, in_size):
-    """-> (mode, S, lead_pad, CI_l, CO_l, K, out_size, widx) of the launch: mode 'corr' (strided correlation with leading zero
-    padding) or 'tconv' (stride-2 transposed convolution, gather form); widx(cin, kd, kh, kw, cout) = flat index of that weight in
-    the layer's own weight tensor (conv: [co][ci][k], convt: [ci][co][k])."""
-    import numpy as np
-    KD, KH, KW = spec.k
-    kvol = KD * KH * KW
-    conv = spec.kind == 'conv'
-
-    def w_at(ci_layer, co_layer, kd, kh, kw):
-        t = (kd * KH + kh) * KW + kw
-        return ((co_layer * spec.ci + ci_layer) if conv else (ci_layer * spec.co + co_layer)) * kvol + t
-    fl = lambda kd, kh, kw: (KD - 1 - kd, KH - 1 - kh, KW - 1 - kw)
-    if direction == 'fwd':
-        osz = spec.out_size(in_size)
-        if conv:
-            return 'corr', spec.stride, (0, 0, 0), spec.ci, spec.co, spec.k, osz, (lambda cin, kd, kh, kw, cout: w_at(cin, cout, kd, kh, kw))
-        if spec.stride == 1:
-            pad = tuple(spec.k[a] - 1 - spec.pad[a] for a in range(3))
-            return 'corr', 1, pad, spec.ci, spec.co, spec.k, osz, (lambda cin, kd, kh, kw, cout: w_at(cin, cout, *fl(kd, kh, kw)))
-        return 'tconv', 2, tuple(spec.pad), spec.ci, spec.co, spec.k, osz, (lambda cin, kd, kh, kw, cout: w_at(cin, cout, kd, kh, kw))
-    # data gradient: in_size is the size of dy (the layer's OUTPUT); the launch writes the layer's input size
-    if conv:
-        isz = None                                                       # caller passes the target size
-        if spec.stride == 1:
-            pad = tuple(spec.k[a] - 1 for a in range(3))
-            return 'corr', 1, pad, spec.co, spec.ci, spec.k, isz, (lambda cin, kd, kh, kw, cout: w_at(cout, cin, *fl(kd, kh, kw)))
-        return 'tconv', 2, (0, 0, 0), spec.co, spec.ci, spec.k, isz, (lambda cin, kd, kh, kw, cout: w_at(cout, cin, kd, kh, kw))
-    return 'corr', spec.stride, tuple(spec.pad), spec.co, spec.ci, spec.k, None, (lambda cin, kd, kh, kw, cout: w_at(cout, cin, kd, kh, kw))
-
-
-_MM_PLANS = {}
-
-
-def mm_plan(spec: ConvSpec, direction: str, in_size, out_size=None, force=None) -> Optional[MmPlan]:
-    """Plan for vg_conv_mm, or None when the launch is not covered (1-channel ends, shapes that do not fit LDS): the caller then
-    uses the register-tiled kernels.  A stride-2 transposed conv with 16 output channels (forward of a convt layer with co == 16,
-    data gradient of a conv layer with ci == 16) is planned as two halves of 8 channels: plan.CO = 16, plan.co_blk = 8.  `in_size`: spatial size of the tensor the launch READS
-    (the layer input for 'fwd', dy for 'bwd'); `out_size`: spatial size it writes (needed for 'bwd')."""
-    import numpy as np
-    key = (spec, direction, tuple(in_size), None if out_size is None else tuple(out_size), force)
-    if key in _MM_PLANS:
-        return _MM_PLANS[key]
-    mode, S, pad, CI, CO, K, osz, widx = _mm_problem(spec, direction, tuple(in_size))
-    if osz is None:
-        osz = tuple(out_size)
-    plan = None
-    if CO in (8, 16) and CI >= 8:
-        plan = _mm_build(mode, S, pad, CI, CO, K, tuple(in_size), tuple(osz), widx, force)
-    _MM_PLANS[key] = plan
-    return plan
-
-
-def _mm_build(mode, S, pad, CI, CO, K, isz, osz, widx, force=None):
-    """force = (PD, cc): tuning sweeps (tools/diag) pin the tile instead of taking the scored choice."""
-    import numpy as np
-    KD, KH, KW = K
-    ID, IH, IW = isz
-    OD, OH, OW = osz
-    IHW = IH * IW
-    # 16 output channels of a stride-2 transposed conv: the w-parity pair needs the two 8-row replicas, so the layer runs as two halves
-    # of 8 channels (a block of the grid owns one half: vg_mm_desc.co_tot), each through the 4-class plan of an 8-channel layer
-    nco = 2 if (mode == 'tconv' and CO == 16) else 1
-    CO_l = CO // nco
-    NR = 16 // CO_l
-    classes = []                                   # per class: list of (dd, dh, dw, tap(rho) -> (kd, kh, kw) or None)
-    if mode == 'corr':
-        KWp = KW + (NR - 1) * S
-        ent = []
-        for kd in range(KD):
-            for kh in range(KH):
-                for kwp in range(KWp):
-                    def tap(rho, kd=kd, kh=kh, kwp=kwp):
-                        kw = kwp - rho * S
-                        return (kd, kh, kw) if 0 <= kw < KW else None
-                    ent.append((kd - pad[0], kh - pad[1], kwp - pad[2], tap))
-        classes.append(ent)
-        PDT, PH, PW = OD, OH, (OW + NR - 1) // NR
-        sdi, shi, swi = S, S, NR * S
-        sdo, sho, swo = 1, 1, NR
-        od0, oh0, ow0 = [0], [0], [0]
-        d0 = -pad[0]
-        ld_of = lambda PD: (PD - 1) * S + KD
-    else:
-        assert NR == 2 and S == 2
-        MDm = (KD + 1) // 2
-        od0, oh0, ow0 = [], [], []
-        for rd, rh in ((0, 0), (0, 1), (1, 0), (1, 1)):
-            if True:
-                ent = []
-                for md in range((KD - rd + 1) // 2):
-                    for mh in range((KH - rh + 1) // 2):
-                        for mw in range(2):
-                            def tap(rho, rd=rd, rh=rh, md=md, mh=mh, mw=mw):
-                                kw = rho + 2 * mw
-                                return (rd + 2 * md, rh + 2 * mh, kw) if kw < KW else None
-                            ent.append((-md, -mh, -mw, tap))
-                classes.append(ent)
-                od0.append(rd - pad[0]); oh0.append(rh - pad[1]); ow0.append(-pad[2])
-        PDT, PH, PW = (OD + pad[0] + 1) // 2, (OH + pad[1] + 1) // 2, (OW + pad[2] + 1) // 2
-        sdi = shi = swi = 1
-        sdo = sho = swo = 2
-        d0 = -(MDm - 1)
-        ld_of = lambda PD: PD + MDm - 1
-    nq = len(classes)
-    if nq not in (1, 4) or any(len(e) == 0 for e in classes):
-        return None
-    ks = [(len(e) + 3) // 4 for e in classes]
-    if max(ks) > 32:
-        return None
-    rows = sum(ks)
-    tau = np.zeros((rows, 4), np.int32); dlt = np.zeros((rows, 4, 3), np.int32)
-    aidx = [[] for _ in range(nco)]                # per channel half: the classes' images back to back
-    slack = 0
-    r0 = 0
-    for q, ent in enumerate(classes):
-        a = -np.ones((nco, CI, ks[q], 64), np.int32)
-        for s in range(ks[q]):
-            for kk in range(4):
-                kap = 4 * s + kk
-                e = ent[kap] if kap < len(ent) else ent[0]               # padding entries: any readable offset, zero weights
-                dd, dh, dw = e[0], e[1], e[2]
-                tau[r0 + s, kk] = dd * IHW + dh * IW + dw
-                dlt[r0 + s, kk] = (dd, dh, dw)
-                slack = max(slack, abs(dh) * IW + abs(dw) + 1)
-                if kap >= len(ent):
-                    continue
-                for row in range(16):
-                    rho, co = row // CO_l, row % CO_l
-                    t = e[3](rho)
-                    if t is None:
-                        continue
-                    lane = kk * 16 + row
-                    for h in range(nco):
-                        for ci in range(CI):
-                            a[h, ci, s, lane] = widx(ci, t[0], t[1], t[2], co + CO_l * h)
-        for h in range(nco):
-            aidx[h].append(a[h].reshape(-1))
-        r0 += ks[q]
-    aidx = np.concatenate([np.concatenate(a) for a in aidx])
-    aimg_blk = aidx.size // nco                    # what a block keeps in LDS: one half's image
-    tpc_max = (8 if max(ks) <= 12 else 3) if nq == 1 else 4        # registers: one operand offset per (tile, k-step)
-    hlo, hhi = int(dlt[:, :, 1].min()), int(dlt[:, :, 1].max())
-    # Tile choice: a block = W waves on PD position planes x PHB position rows (x all PW columns).  Measured (tools/diag/mm_sweep.py,
-    # MI355X): what pays is SEVERAL co-resident blocks per CU -- their input waits, prologues, barriers and epilogues interleave with
-    # each other's matrix phases -- i.e. a small LDS footprint (single-buffered input, row slabs instead of whole planes) and at most
-    # 3 tiles per wave (the 128-register instances: 4 waves per SIMD); then full accumulator columns, a small halo and large channel
-    # chunks.  _MM_TUNED pins the bench geometries where the sweep found a better tile than this score.
-    tuned = _MM_TUNED.get((mode, S, CI, CO, tuple(K), tuple(isz), tuple(osz))) if force is None else None
-    pin = force or tuned
-    cands = []
-    for W in (8, 4):
-        for PD in range(min(PDT, 16), 0, -1):
-            LD = ld_of(PD)
-            for nslab in (1, 2, 3, 4, 6, 8, 12):
-                PHB = (PH + nslab - 1) // nslab
-                if nslab > 1 and ((PH + PHB - 1) // PHB != nslab or PHB < 2):
-                    continue
-                npos = PD * PHB * PW
-                tpc = (npos + W * 16 - 1) // (W * 16)
-                if tpc > tpc_max:
-                    continue
-                rows_max = min((PHB - 1) * shi + (hhi - hlo) + 1, IH)
-                whole = (nslab == 1 and hlo <= 0 and (PH - 1) * shi + hhi + 1 >= IH)
-                LPH = IHW if whole else ((rows_max * IW + 3) // 4) * 4 + 4
-                CHP = 64 + ((LD * LPH + 63) // 64) * 64
-                bps = ((PDT + PD - 1) // PD) * nslab
-                for cc in ([CI] if nq > 1 else [c for c in range(CI, 0, -1) if CI % c == 0]):
-                    for dbuf in (1, 0):
-                        if pin and (W, PD, PHB, cc, dbuf) != tuple(pin):
-                            continue
-                        lds = (((aimg_blk + 63) // 64) * 64 + rows * 64 + (1 + dbuf) * cc * CHP + 64) * 4
-                        if lds > _MM_LDS_BUDGET:
-                            continue
-                        per_simd = 4 if (tpc <= 3 or nq > 1) else 2                               # waves per SIMD the instance's registers allow
-                        nblk = min(_MM_LDS_CU // lds, per_simd * 4 // W)
-                        if nblk < 1:
-                            continue
-                        util = npos / float(tpc * W * 16) * (PDT / float(((PDT + PD - 1) // PD) * PD)) * (PH / float(nslab * PHB))   # filled accumulator columns
-                        halo = ((PD * sdi) / float(LD)) * min(1.0, (PHB * shi) / float(rows_max))        # useful share of the staged elements
-                        wps = nblk * W // 4                                                        # co-resident waves per SIMD
-                        occ = {1: 0.45, 2: 0.6, 3: 0.8}.get(wps, 1.0)
-                        # whole planes in 8-wave blocks measured best wherever they fit (41x49x35: row slabs / 4-wave blocks 3-20 % slower:
-                        # more halo rows, fewer waves to balance a block's tiles over); slabs are what lets the 82x98x70 planes in at all
-                        shape = (1.0 if nslab == 1 else 0.85) * (1.0 if W == 8 else 0.9)
-                        score = util * (0.5 + 0.5 * halo) * (0.9 + 0.1 * cc / float(CI)) * occ * shape * (1.0 if (dbuf or nblk >= 2) else 0.9)
-                        cands.append((score, PD, LD, cc, tpc, dbuf, PHB, W))
-    if not cands:
-        return None
-    _, PD, LD, cc, tpc, dbuf, PHB, W = max(cands, key=lambda c: (round(c[0], 9), c[3], -c[5]))
-    tpc = {1: (3 if tpc <= 3 else tpc if tpc <= 6 else 8), 4: 4}[nq]
-    return MmPlan(CI=CI, CO=CO, co_blk=CO_l, ID=ID, IH=IH, IW=IW, OD=OD, OH=OH, OW=OW, nq=nq, ks=ks, PDT=PDT, PH=PH, PW=PW, PD=PD, sdi=sdi, shi=shi,
-                  swi=swi, d0=d0, LD=LD, cc=cc, sdo=sdo, sho=sho, swo=swo, od0=od0, oh0=oh0, ow0=ow0, tpc=tpc, slack=slack, dbuf=dbuf,
-                  PHB=PHB, hlo=hlo, hhi=hhi, waves=W,
-                  tau=tau.reshape(-1), dlt=dlt.reshape(-1), aidx=aidx, mode=mode)
+# --------------------------------------------------------------------------- matrix-core convolution (vg_conv_mm; plans: conv_mm_plan.py)
+USE_MM = int(_os.environ.get('VG_CONV_MM', '1'))            # 0: off; 1: where it measured faster (mm_wins); 2: wherever a plan exists
 
 
 def conv_mm(x, plan: MmPlan, aimg, bias, relu_in, scale, shift, per_group, mask_src=None, next_bn=None, relu_out=False, stats_like=None):
@@ -1699,20 +1391,18 @@ def conv_mm(x, plan: MmPlan, aimg, bias, relu_in, scale, shift, per_group, mask_
     d = plan.desc(N, relu_in, per_group if scale is not None else 1, relu_out)
     y = torch.empty((N, plan.CO, plan.OD, plan.OH, plan.OW), dtype=torch.float32, device=x.device)
     _chk(x); _chk(aimg)
-    if next_bn and stats_like is not None:
-        _call(x, 'vg_conv_mm', ctypes.byref(d), _p(x), _p(aimg), _p(tau), _p(dlt), _p(bias), _p(scale), _p(shift), _p(mask_src), _p(y), 1, 0, None)
+    part, stats = None, (1, 0, None)                         # (statistics per_group, statistics on, partials) of the epilogue
+    if next_bn and stats_like is None:
+        chunks = lib.size('vg_conv_mm_stats_chunks', ctypes.byref(d), int(next_bn))
+        part = torch.zeros((N // int(next_bn)) * plan.CO * chunks * 2, dtype=torch.float64, device=x.device)
+        stats = (int(next_bn), 1, _p(part))
+    _call(x, 'vg_conv_mm', ctypes.byref(d), _p(x), _p(aimg), _p(tau), _p(dlt), _p(bias), _p(scale), _p(shift), _p(mask_src), _p(y), *stats)
+    if not next_bn:
+        return y
+    if stats_like is not None:
         _, cd, osz = conv_fwd_desc(stats_like, N, (plan.ID, plan.IH, plan.IW), relu_in, per_group if scale is not None else 1, relu_out)
         assert tuple(osz) == (plan.OD, plan.OH, plan.OW) and stats_like.co == plan.CO
         chunks = lib.size('vg_tconv3d_s2_stats_chunks', ctypes.byref(cd), int(next_bn))
         part = torch.empty((N // int(next_bn)) * plan.CO * chunks * 2, dtype=torch.float64, device=x.device)
         _call(x, 'vg_tconv3d_s2_stats_of', ctypes.byref(cd), _p(y), int(next_bn), 1, _p(part))
-        return y, part
-    if next_bn:
-        chunks = lib.size('vg_conv_mm_stats_chunks', ctypes.byref(d), int(next_bn))
-        G = N // int(next_bn)
-        part = torch.zeros(G * plan.CO * chunks * 2, dtype=torch.float64, device=x.device)
-        _call(x, 'vg_conv_mm', ctypes.byref(d), _p(x), _p(aimg), _p(tau), _p(dlt), _p(bias), _p(scale), _p(shift), _p(mask_src), _p(y),
-              int(next_bn), 1, _p(part))
-        return y, part
-    _call(x, 'vg_conv_mm', ctypes.byref(d), _p(x), _p(aimg), _p(tau), _p(dlt), _p(bias), _p(scale), _p(shift), _p(mask_src), _p(y), 1, 0, None)
-    return y
+    return y, part

@@ -324,8 +324,8 @@ class VAE(nn.Module):
         matrix-core plans were built by PackedWeights; a layer without one runs on the register-tiled kernels.)
         The constructor asks with a batch of 2, which settles what depends on the shape alone (LDS tiles, row widths); the
         weight-gradient planner also weighs the batch when it picks a tile, so forward_core asks again with the batch of the step,
-        once per batch size, before that step's first launch.  With VG_FUSE_LAST_BN_BWD=0 the last stage takes the unfused batch-norm
-        backward, which has no planner of its own and has been run on the explicit shapes only."""
+        once per batch size, before that step's first launch.  The last stage is asked for the fused batch-norm backward it takes
+        (ops.fuse_last_bn_bwd); the unfused one, which a last stage of another shape would take, has no planner of its own."""
         import ctypes
         from . import _lib
         lib = _lib.get_lib()                          # a missing library says so itself
@@ -342,7 +342,7 @@ class VAE(nn.Module):
                 if sp.name in with_bn:
                     ops.bn_plan(n, sp.ci, int(np.prod(isz)), B)
                     lib.size('vg_bn_ws_bytes', n, sp.ci, int(np.prod(isz)), B)
-                if sp.name == 'convt5' and ops.FUSE_LAST_BN_BWD:      # bnt5's backward fused with convt5's data gradient stages planes of dy
+                if sp.name == 'convt5' and ops.fuse_last_bn_bwd(sp):  # bnt5's backward fused with convt5's data gradient stages planes of dy
                     lib.size('vg_bn_tconv1_lds_bytes', sp.ci, *isz)
                     lib.size('vg_bn_tconv1_ws_bytes', n, sp.ci, isz[0], B)
             except _lib.VgError as e:
