@@ -370,6 +370,16 @@ int vg_loss_bwd(const float* g_loss, int32_t B, int32_t CB, double c_kl, double 
  *   ws: vg_knn_ws_bytes(N, D, k) bytes of device scratch (may be NULL when that is 0). */
 int64_t vg_knn_ws_bytes(int32_t N, int32_t D, int32_t k);
 int vg_knn(const float* x, int32_t N, int32_t D, int32_t k, void* ws, int32_t* idx, float* dist, void* stream);
+/* What vg_knn launches for (N, D, k), from the planner vg_knn and vg_knn_ws_bytes use: host only, nothing is launched, no memory is
+ * touched.  out[0 .. VG_KNN_PLAN_LEN):
+ *   KB (places of the register list of the instance launched: 8, 16, 32 or 64 for k-1 <= KB; 0 when k = 1, where only the merge
+ *   kernel runs and writes position 0), S (candidate splits launched: the grid's y of the partial kernel), chunk (candidates per
+ *   split, a multiple of 16), Dp (D padded to a multiple of 16), query blocks (of 256 queries: the grid's x of both kernels),
+ *   candidates in the last split (N - (S-1)*chunk), dynamic LDS bytes of the partial kernel (0 when KB = 0).
+ * The workspace is S*(k-1)*N*8 bytes.  n_out < VG_KNN_PLAN_LEN (or out NULL) returns VG_ERR_ARG; a shape vg_knn_ws_bytes answers -1
+ * for returns VG_ERR_ARG and leaves the same kind of text in vg_last_error(). */
+#define VG_KNN_PLAN_LEN 7
+int vg_knn_plan(int32_t N, int32_t D, int32_t k, int32_t* out, int32_t n_out);
 
 /* Fuzzy simplicial set of each neighbour row (umap-learn smooth_knn_dist + compute_membership_strengths, local_connectivity 1,
  * bandwidth 1), in fp64: rho_i = smallest non-zero dist in row i (0 if none); sigma_i by at most 64 bisection steps to

@@ -93,6 +93,7 @@ _PROTOS = {
     'vg_loss_bwd': (ctypes.c_int, [vp, i32, i32, f64, f64, f64, f64, vp, vp, vp, vp, vp]),
     'vg_knn_ws_bytes': (i64, [i32, i32, i32]),
     'vg_knn': (ctypes.c_int, [vp, i32, i32, i32, vp, vp, vp, vp]),
+    'vg_knn_plan': (ctypes.c_int, [i32, i32, i32, ctypes.POINTER(i32), i32]),
     'vg_umap_fuzzy': (ctypes.c_int, [vp, vp, i32, i32, vp, vp, vp, vp, vp]),
     'vg_umap_layout_epoch': (ctypes.c_int, [vp, vp, vp, vp, i32, i32, i32, i32, f64, f64, i32, ctypes.c_uint64, vp, vp]),
     'vg_channel_sum': (ctypes.c_int, [vp, i32, i32, i64, vp, vp, i32, vp]),
@@ -143,6 +144,7 @@ FC_PLAN_JOB_FIELDS = ('a_vec', 'b_vec', 'big', 'kchunk', 'gx', 'gy', 'first', 'b
 GAIN_PLAN_FIELDS = ('path', 'threads', 'panel', 'npanels', 'last_panel', 'slab', 'nslabs', 'last_slab', 'lds_fwd', 'lds_bwd',
                     'launches_fwd', 'launches_bwd')                                                          # VG_GAIN_PLAN_LEN, in order
 GAIN_PATHS = ('lds', 'blocked', 'tiled')                                                                    # values of field 0
+KNN_PLAN_FIELDS = ('KB', 'S', 'chunk', 'Dp', 'qblocks', 'last', 'lds_bytes')                                # VG_KNN_PLAN_LEN, in order
 GUARD_STATE_LEN = 8           # VG_GUARD_STATE_LEN: [total_norm, scale, apply, seen, skipped, clipped, norm_sum, norm_max]
 EXPORTS = tuple(_PROTOS)
 

@@ -154,6 +154,7 @@ extern "C" int vg_loss_bwd(const float* g_loss, int32_t B, int32_t CB, double c_
 // host side (graph union, spectral init, the epoch loop) is vae_gam_amd/latent_projection.py.  None of this runs in the train step.
 #include <climits>
 #include <math.h>
+#include "../../include/vaegam.h"                       // VG_KNN_PLAN_LEN
 
 namespace {
 
@@ -264,15 +265,6 @@ knn_merge_k(const float* __restrict__ ws_d, const int* __restrict__ ws_i, int N,
         if (m < K1) { idx[r + 1 + m] = knn_key_idx(kl[m]); dist[r + 1 + m] = knn_key_dist(kl[m]); }
 }
 
-template <int KB>
-void knn_launch(const float* x, int N, int D, int K1, float* ws_d, int* ws_i, int S, int chunk, int32_t* idx, float* dist, hipStream_t s) {
-    const int Dp = vg_cdiv(D, KNN_DC) * KNN_DC;
-    if (K1 > 0)
-        vg_launch(knn_partial_k<KB>, dim3(vg_cdiv(N, KNN_Q), S), dim3(KNN_Q), (size_t)KNN_TC * (Dp + KNN_Q) * sizeof(float), s, x, N, D, Dp, K1,
-                  chunk, ws_d, ws_i);
-    vg_launch(knn_merge_k<KB>, dim3(vg_cdiv(N, 256)), dim3(256), 0, s, (const float*)ws_d, (const int*)ws_i, N, K1, S, idx, dist);
-}
-
 // candidate splits: enough blocks to fill the CUs at large N (~2048), at least 128 candidates per split, at most 16 splits
 void knn_splits(int N, int* S, int* chunk) {
     const int qt = vg_cdiv(N, KNN_Q);
@@ -280,6 +272,30 @@ void knn_splits(int N, int* S, int* chunk) {
     s = s < 1 ? 1 : (s > 16 ? 16 : s);
     *chunk = vg_cdiv(vg_cdiv(N, s), KNN_TC) * KNN_TC;
     *S = vg_cdiv(N, *chunk);
+}
+
+// every launch decision of vg_knn, in the order vg_knn_plan reports it; vg_knn_ws_bytes sizes the workspace from the same record
+struct KnnPlan { int KB, S, chunk, Dp, qblocks, last, lds; };
+
+bool knn_shape_ok(int N, int D, int k) { return N > 0 && D >= 1 && D <= 128 && k >= 1 && k <= 64 && k <= N; }
+
+KnnPlan knn_plan(int N, int D, int k) {
+    KnnPlan p;
+    const int K1 = k - 1;
+    p.KB = K1 == 0 ? 0 : (K1 <= 8 ? 8 : (K1 <= 16 ? 16 : (K1 <= 32 ? 32 : 64)));
+    knn_splits(N, &p.S, &p.chunk);
+    p.Dp = vg_cdiv(D, KNN_DC) * KNN_DC;
+    p.qblocks = vg_cdiv(N, KNN_Q);
+    p.last = N - (p.S - 1) * p.chunk;
+    p.lds = p.KB ? KNN_TC * (p.Dp + KNN_Q) * (int)sizeof(float) : 0;
+    return p;
+}
+
+template <int KB>
+void knn_launch(const float* x, int N, int D, int K1, float* ws_d, int* ws_i, const KnnPlan& p, int32_t* idx, float* dist, hipStream_t s) {
+    if (p.KB)
+        vg_launch(knn_partial_k<KB>, dim3(p.qblocks, p.S), dim3(KNN_Q), (size_t)p.lds, s, x, N, D, p.Dp, K1, p.chunk, ws_d, ws_i);
+    vg_launch(knn_merge_k<KB>, dim3(p.qblocks), dim3(KNN_Q), 0, s, (const float*)ws_d, (const int*)ws_i, N, K1, p.S, idx, dist);
 }
 
 constexpr int FZ_PARTS = 256;   // blocks of the fixed-order global mean
@@ -400,25 +416,31 @@ umap_layout_k(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ co
 }  // namespace
 
 extern "C" int64_t vg_knn_ws_bytes(int32_t N, int32_t D, int32_t k) {
-    if (N <= 0 || D < 1 || D > 128 || k < 1 || k > 64 || k > N) { vg_set_error("vg_knn_ws_bytes: bad shape (N %d, D %d, k %d)", N, D, k); return -1; }
-    int S, chunk;
-    knn_splits(N, &S, &chunk);
-    return (int64_t)S * (k - 1) * N * 8;
+    if (!knn_shape_ok(N, D, k)) { vg_set_error("vg_knn_ws_bytes: bad shape (N %d, D %d, k %d)", N, D, k); return -1; }
+    return (int64_t)knn_plan(N, D, k).S * (k - 1) * N * 8;
+}
+
+extern "C" int vg_knn_plan(int32_t N, int32_t D, int32_t k, int32_t* out, int32_t n_out) {
+    if (!out || n_out < VG_KNN_PLAN_LEN) { vg_set_error("vg_knn_plan: out must hold %d values", VG_KNN_PLAN_LEN); return VG_ERR_ARG; }
+    if (!knn_shape_ok(N, D, k)) { vg_set_error("vg_knn_plan: bad shape (N %d, D %d, k %d)", N, D, k); return VG_ERR_ARG; }
+    const KnnPlan p = knn_plan(N, D, k);
+    const int v[VG_KNN_PLAN_LEN] = {p.KB, p.S, p.chunk, p.Dp, p.qblocks, p.last, p.lds};
+    for (int i = 0; i < VG_KNN_PLAN_LEN; ++i) out[i] = v[i];
+    return VG_OK;
 }
 
 extern "C" int vg_knn(const float* x, int32_t N, int32_t D, int32_t k, void* ws, int32_t* idx, float* dist, void* stream) {
     if (!x || !idx || !dist || (k > 1 && !ws)) { vg_set_error("vg_knn: null argument"); return VG_ERR_ARG; }
-    if (N <= 0 || D < 1 || D > 128 || k < 1 || k > 64 || k > N || (int64_t)N * k > INT_MAX) { vg_set_error("vg_knn: bad shape (N %d, D %d, k %d)", N, D, k); return VG_ERR_ARG; }
-    int S, chunk;
-    knn_splits(N, &S, &chunk);
+    if (!knn_shape_ok(N, D, k) || (int64_t)N * k > INT_MAX) { vg_set_error("vg_knn: bad shape (N %d, D %d, k %d)", N, D, k); return VG_ERR_ARG; }
+    const KnnPlan p = knn_plan(N, D, k);
     const int K1 = k - 1;
     float* ws_d = (float*)ws;
-    int* ws_i = ws ? (int*)((char*)ws + (size_t)S * K1 * N * 4) : nullptr;
+    int* ws_i = ws ? (int*)((char*)ws + (size_t)p.S * K1 * N * 4) : nullptr;
     hipStream_t s = (hipStream_t)stream;
-    if (K1 <= 8) knn_launch<8>(x, N, D, K1, ws_d, ws_i, S, chunk, idx, dist, s);
-    else if (K1 <= 16) knn_launch<16>(x, N, D, K1, ws_d, ws_i, S, chunk, idx, dist, s);
-    else if (K1 <= 32) knn_launch<32>(x, N, D, K1, ws_d, ws_i, S, chunk, idx, dist, s);
-    else knn_launch<64>(x, N, D, K1, ws_d, ws_i, S, chunk, idx, dist, s);
+    if (p.KB <= 8) knn_launch<8>(x, N, D, K1, ws_d, ws_i, p, idx, dist, s);      // KB = 0 (k = 1): the merge alone, position 0
+    else if (p.KB == 16) knn_launch<16>(x, N, D, K1, ws_d, ws_i, p, idx, dist, s);
+    else if (p.KB == 32) knn_launch<32>(x, N, D, K1, ws_d, ws_i, p, idx, dist, s);
+    else knn_launch<64>(x, N, D, K1, ws_d, ws_i, p, idx, dist, s);
     return vg_check_launch("knn");
 }
 

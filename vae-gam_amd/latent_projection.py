@@ -9,6 +9,9 @@ The rest is plumbing: the union of the fuzzy sets and the CSR graph (torch on th
 initialisation (scipy on the host, float64, once).  Deliberate differences to umap-learn: the epoch is a Jacobi
 update (every contribution of epoch n reads Y_n), and every due edge draws exactly `negative_sample_rate` negatives.
 """
+import ctypes
+from collections import namedtuple
+
 import numpy as np
 import torch
 
@@ -19,6 +22,18 @@ from .ops import _call, _p
 def default_n_epochs(n):
     """umap-learn's rule: 500 epochs up to 10,000 points, 200 above."""
     return 500 if n <= 10000 else 200
+
+
+KnnPlan = namedtuple('KnnPlan', _lib.KNN_PLAN_FIELDS)
+
+
+def knn_plan(N, D, k) -> KnnPlan:
+    """What knn launches for N points of D dimensions and k neighbours, from vg_knn's own planner (vg_knn_plan): nothing is launched.
+    KB: places of the register list of the kernel instance (0: k = 1, no partial launch), S splits of `chunk` candidates, `last` of them
+    in the last split, Dp the padded D, qblocks blocks of 256 queries, lds_bytes of the partial kernel.  A bad shape raises VgError."""
+    rec = (ctypes.c_int32 * len(KnnPlan._fields))()
+    _lib.get_lib().call('vg_knn_plan', int(N), int(D), int(k), rec, len(rec))
+    return KnnPlan(*rec)
 
 
 def knn(latent, k):
