@@ -328,6 +328,46 @@ int32_t vg_gam_stats_slots(int32_t C);
 int vg_gam_stats_accumulate(const float* logits, const float* gain, const float* x, const int32_t* subj, const uint8_t* mask,
                             int32_t C, int32_t B, int32_t S, const int32_t* nat, const int32_t* grid, double* acc, void* stream);
 
+/* Sign-flip permutation test with the max-statistic (an extension; host side: MapStatistics.group_permutation): family-wise-error
+ * corrected inference on a one-sample map over S subjects, 2 <= S <= 64, without ever forming the [P][V] array of statistics.
+ *   m double [S][V]: the subject values;  scale double [V]: 1 / sqrt(S * sum_s m[s][v]^2), formed by the caller; a voxel whose scale is
+ *   not > 0 takes no part;  signs uint64 [P]: bit s of word p set flips subject s in permutation p;  tail 0: two-sided, 1: positive,
+ *   2: negative;  ws: vg_signflip_ws_bytes(S, V, P) bytes of device scratch.
+ * Per permutation p and voxel v, in fp64:
+ *   T_p[v] = +0.0, then for s = 0 .. S-1 in that order T = T + (bit s of signs[p] ? -m[s][v] : m[s][v])   (adds only; the sign is
+ *   applied exactly, as a multiplication by +-1.0: fused with the add or not, the same bits);
+ *   u_p[v] = T_p[v] * scale[v]   (one multiplication; u = t / sqrt(S - 1 + t^2) is strictly increasing in the one-sample t, so ranks
+ *   and p-values are those of t);  g(u) = |u| (tail 0), u (tail 1), -u (tail 2), and g' the same function applied to T itself.
+ * Outputs:
+ *   stat0 [V]    g(T_id[v] * scale[v]) with T_id the sum without flips (formed apart from the sign list); 0 for a voxel taking no part;
+ *   maxstat [P]  max over the voxels that take part of g(u_p[v]); a -0.0 enters the maximum as +0.0, so its bits are defined; a voxel
+ *                that takes no part adds nothing (not a 0 either: a one-sided maximum of negative values stays negative); with no
+ *                voxel taking part at all: -inf;
+ *   cnt_unc [V]  int32, the number of p with g'(T_p[v]) >= g'(T_id[v]): compared on the unscaled sums, no rounding involved; P for a
+ *                voxel taking no part.
+ * m and scale are expected finite.  One lane owns one voxel and keeps its S values in registers; the grid is voxel tiles x chunks of
+ * permutations; per-tile maxima and per-chunk counts go to ws and a second launch folds them.  No atomics: two runs give the same bits.
+ * Refused, nothing written: null pointers, S < 2, V <= 0, V >= 2^31, P <= 0, P > 2^20, tail outside 0..2 (VG_ERR_ARG); S > 64
+ * (VG_ERR_UNSUPPORTED).  vg_signflip_ws_bytes answers -1 for every refused shape. */
+int64_t vg_signflip_ws_bytes(int32_t S, int64_t V, int32_t P);
+int vg_signflip_maxstat(const double* m, const double* scale, const uint64_t* signs, int32_t S, int64_t V, int32_t P, int32_t tail,
+                        void* ws, double* stat0, double* maxstat, int32_t* cnt_unc, void* stream);
+/* What vg_signflip_maxstat launches for (S, V, P), from the planner it and vg_signflip_ws_bytes use: host only, nothing is launched, no
+ * memory is touched.  out[0 .. VG_SIGNFLIP_PLAN_LEN):
+ *   0 SMAX          places of the register array of the instance launched: 8, 16, 32 or 64 for S <= SMAX
+ *   1 lanes         lanes per block = voxels per tile (256)
+ *   2 tiles         voxel tiles: ceil(V / lanes)
+ *   3 chunk         permutations per chunk (a multiple of 16, at least 64; the last chunk holds the rest)
+ *   4 chunks        ceil(P / chunk)
+ *   5 grid_x, 6 grid_y   of the main launch (tiles, chunks)
+ *   7 fold_blocks   grid of the fold launch: ceil(P / lanes) blocks for maxstat, then tiles blocks for cnt_unc
+ *   8 lds_bytes     static LDS of the main kernel
+ *   9 ws_lo, 10 ws_hi    the workspace bytes, ws_lo + (ws_hi << 31) = tiles * P * 8 (maxima) + chunks * V * 4 (counts)
+ * n_out < VG_SIGNFLIP_PLAN_LEN (or out NULL) returns VG_ERR_ARG; a shape vg_signflip_ws_bytes answers -1 for returns the status
+ * vg_signflip_maxstat would and leaves the same kind of text in vg_last_error(). */
+#define VG_SIGNFLIP_PLAN_LEN 11
+int vg_signflip_plan(int32_t S, int64_t V, int32_t P, int32_t* out, int32_t n_out);
+
 /* Batch-norm parameter gradients from vg_bn_bwd_reduce's per-(group, channel) sums:
  *   dgamma[c] (+)= sum_g sums[g][c][1],  dbeta[c] (+)= sum_g sums[g][c][0]   (accumulate != 0 adds into the .grad buffers;
  *   replaces autograd's sum + add launches after torch.nn.BatchNorm3d's backward, vae_reg_GP.py:195-201,216-222). */

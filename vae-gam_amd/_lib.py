@@ -109,6 +109,9 @@ _PROTOS = {
                                               vp, vp, i32, vp]),
     'vg_gam_stats_slots': (i32, [i32]),
     'vg_gam_stats_accumulate': (ctypes.c_int, [vp, vp, vp, vp, vp, i32, i32, i32, ctypes.POINTER(i32), ctypes.POINTER(i32), vp, vp]),
+    'vg_signflip_ws_bytes': (i64, [i32, i64, i32]),
+    'vg_signflip_maxstat': (ctypes.c_int, [vp, vp, vp, i32, i64, i32, i32, vp, vp, vp, vp, vp]),
+    'vg_signflip_plan': (ctypes.c_int, [i32, i64, i32, ctypes.POINTER(i32), i32]),
     'vg_pack_weights': (ctypes.c_int, [vp, vp, vp, i32, i64, vp]),
     'vg_cholesky_f64': (ctypes.c_int, [vp, vp, i32, i32, vp]),
     'vg_conv_mm_stats_chunks': (i64, [ctypes.POINTER(MmDesc), i32]),
@@ -145,7 +148,9 @@ GAIN_PLAN_FIELDS = ('path', 'threads', 'panel', 'npanels', 'last_panel', 'slab',
                     'launches_fwd', 'launches_bwd')                                                          # VG_GAIN_PLAN_LEN, in order
 GAIN_PATHS = ('lds', 'blocked', 'tiled')                                                                    # values of field 0
 KNN_PLAN_FIELDS = ('KB', 'S', 'chunk', 'Dp', 'qblocks', 'last', 'lds_bytes')                                # VG_KNN_PLAN_LEN, in order
-GUARD_STATE_LEN = 8           # VG_GUARD_STATE_LEN: [total_norm, scale, apply, seen, skipped, clipped, norm_sum, norm_max]
+SIGNFLIP_PLAN_FIELDS = ('SMAX', 'lanes', 'tiles', 'chunk', 'chunks', 'grid_x', 'grid_y', 'fold_blocks', 'lds_bytes', 'ws_lo', 'ws_hi')   # VG_SIGNFLIP_PLAN_LEN
+SIGNFLIP_TAILS = ('two', 'pos', 'neg')                                                                      # the tail argument, by value
+GUARD_STATE_LEN = 8          # VG_GUARD_STATE_LEN: [total_norm, scale, apply, seen, skipped, clipped, norm_sum, norm_max]
 EXPORTS = tuple(_PROTOS)
 
 

@@ -12,6 +12,7 @@ import numpy as np
 import pandas as pd
 
 from . import nifti
+from .map_statistics import NoVoxelError
 
 MAPS_ALL = ['base', 'task', 'full_rec', 'x_mot', 'y_mot', 'z_mot', 'pitch_mot', 'roll_mot', 'yaw_mot', 'sex']   # :66-67
 
@@ -67,12 +68,17 @@ def _ref_or_none(ref_niis, i):
     return ref_niis[i] if ok else None
 
 
-def mk_stat_maps(csv_file, model, save_dir, loader, mk_motion_maps=False, at_mean=False):
+def mk_stat_maps(csv_file, model, save_dir, loader, mk_motion_maps=False, at_mean=False, n_perm=0, perm_seed=0):
     """Voxel-wise statistics next to the averages (an extension; VAE.map_statistics): under
     reconstructions/<ckpt>_stat_model_recons/, per subject `<map>_std.nii` (standard deviation of the map over the subject's volumes),
     `r2.nii` (variance of the data the model explains) and `<covariate map>_partial_r2.nii`; at top level `<map>_t.nii` (one-sample t
     over the subject means) and `r2_avg.nii` (mean of the subjects' r2).  Reference geometry and map selection as mk_avg_maps; one
-    pass over `loader`, nothing is read back from the per-volume files.  Returns the MapStatistics."""
+    pass over `loader`, nothing is read back from the per-volume files.  Returns the MapStatistics.
+    n_perm > 0 adds group inference on every `<map>_t.nii` (MapStatistics.group_permutation: two-sided sign-flip permutation test with
+    the max-statistic, n_perm sign patterns or all 2^S of them, seeded by perm_seed): `<map>_fwe_1mp.nii` and `<map>_unc_1mp.nii` hold
+    1 - p, family-wise-error corrected and uncorrected (the convention of FSL randomise: large is significant; a voxel that takes no
+    part has p = 1, so exactly 0), and `perm_thresholds.csv` lists per map the tail, the number of patterns P, whether they were exhaustive, the
+    critical |t| at family-wise level 0.05 and the number of voxels with a corrected p <= 0.05."""
     subjs, ref_niis = _subjects(csv_file)
     stats = model.map_statistics(loader, num_subjects=len(subjs), at_mean=at_mean)
     ckpt_num = str(model.epoch).zfill(3)
@@ -98,4 +104,21 @@ def mk_stat_maps(csv_file, model, save_dir, loader, mk_motion_maps=False, at_mea
     for m in maps:
         nifti.write_nifti1(os.path.join(stat_dir, '{}_t.nii'.format(m)), host(stats.group_t(m)).reshape(shape), ref0)
     nifti.write_nifti1(os.path.join(stat_dir, 'r2_avg.nii'), host(stats.group_r2()).reshape(shape), ref0)
+    if n_perm > 0:
+        rows = []
+        for m in maps:
+            try:
+                perm = stats.group_permutation(m, n_perm=n_perm, seed=perm_seed, tail='two')
+            except NoVoxelError:                                                         # (a map that is the same in every subject: nothing to test)
+                zero = np.zeros(shape)
+                nifti.write_nifti1(os.path.join(stat_dir, '{}_fwe_1mp.nii'.format(m)), zero, ref0)
+                nifti.write_nifti1(os.path.join(stat_dir, '{}_unc_1mp.nii'.format(m)), zero, ref0)
+                rows.append({'map': m, 'tail': 'two', 'P': 0, 'exhaustive': False, 't_crit_0.05': float('nan'), 'n_fwe_0.05': 0})
+                continue
+            nifti.write_nifti1(os.path.join(stat_dir, '{}_fwe_1mp.nii'.format(m)), host(1.0 - perm.p_fwe).reshape(shape), ref0)
+            nifti.write_nifti1(os.path.join(stat_dir, '{}_unc_1mp.nii'.format(m)), host(1.0 - perm.p_unc).reshape(shape), ref0)
+            rows.append({'map': m, 'tail': perm.tail, 'P': perm.n_perm, 'exhaustive': perm.exhaustive, 't_crit_0.05': perm.threshold(0.05),
+                         'n_fwe_0.05': int((perm.p_fwe <= 0.05).sum())})
+        pd.DataFrame(rows, columns=['map', 'tail', 'P', 'exhaustive', 't_crit_0.05', 'n_fwe_0.05']).to_csv(
+            os.path.join(stat_dir, 'perm_thresholds.csv'), index=False)
     return stats

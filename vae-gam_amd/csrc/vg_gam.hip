@@ -11,6 +11,7 @@
 // Three entry-point pairs share the two kernels through compile-time flags: the plain pair (everything on one grid), the _embed pair
 // (logits on a larger grid than the data; the padding takes no part) and the _masked pair (a voxel mask on the data's grid, with or
 // without embedding; a voxel outside the mask takes no part, exactly like the padding).
+#include <type_traits>
 #include "vg_common.h"
 #include "../../include/vaegam.h"
 
@@ -595,6 +596,163 @@ pack_weights_k(const float* __restrict__ flat, float* __restrict__ packed, const
     }
 }
 
+// ---------------------------------------------------------------------------------- sign-flip permutation test, max-statistic
+// One lane owns one voxel: its S subject means sit in registers (mv[], indexed by constants only), and the lane walks the sign words of
+// its block's permutation chunk.  Per permutation p (include/vaegam.h has the statistic to the bit):
+//   T = +0.0;  for s ascending: T = T + sg * m[s]   (sg = -1.0 where bit s of the word is set, else 1.0: the product is exact, so the
+//   fused and the unfused form give the same bits);  g = tail(T * scale);  count += tail(T) >= tail(T_id).
+// The words are wave-uniform: read through the constant address space (scalar loads), each sign is a scalar select between the two
+// inline constants and reaches the vector ALU as the scalar operand of one v_fma_f64 per subject and permutation.  SF_PU permutations
+// run side by side (independent chains), subjects go in groups of 4 behind one scalar test of S (the means beyond S are 0.0, which
+// changes no bit of T: T is never -0.0).
+// The maximum over the block's voxels, per permutation, goes through LDS SF_PB permutations at a time: every lane writes its g (a lane
+// without a live voxel: -inf) into tile[perm][lane]; then thread t folds 16 interleaved voxels of permutation t / 16 and the 16 threads
+// of a permutation finish by four shuffles.  Row pitch 272 doubles: the two permutations a half-wave reads sit 32 banks apart.
+// No floating-point atomics, no atomics at all: part_max[tile][p] and part_cnt[chunk][v] are folded by signflip_fold_k.
+constexpr int SF_T = 256;        // lanes per block = voxels per tile
+constexpr int SF_PB = 16;        // permutations per trip through LDS
+constexpr int SF_PU = 4;         // permutations whose sums run side by side
+constexpr int SF_PITCH = SF_T + 16;
+constexpr int SF_MIN_CHUNK = 64; // fewest permutations a block walks (but for the last chunk)
+constexpr int SF_BLOCKS = 2048;  // blocks the planner aims at: 8 per CU
+
+#ifdef VG_EMU
+typedef const unsigned long long* sf_words;
+static inline double sf_max(double a, double b) { return a > b ? a : b; }
+#else
+typedef const __attribute__((address_space(4))) unsigned long long* sf_words;
+// one v_max_f64; the same value as the host form: no operand is a nan, and no -0.0 reaches a maximum (signflip_k)
+__device__ __forceinline__ double sf_max(double a, double b) { return fmax(a, b); }
+#endif
+#define SF_NEG_INF (-__builtin_inf())
+
+// -1.0 where bit SB of the (wave-uniform) word is set, else 1.0.  On the GPU as two scalar instructions, a bit test and a select of two
+// inline constants into a register pair, which is then the scalar operand of one v_fma_f64: written in C++ the compiler sees through
+// the +-1.0 and turns sg * m into a per-lane select of -m or m (a lane mask, a v_cndmask and an add per subject and permutation).
+// volatile keeps each select next to its fma: free to hoist them, the scheduler holds more pairs than the SMAX = 64 instance has scalar
+// registers for (5 scalar spills).
+#ifdef VG_EMU
+template <int SB> static inline double sf_sign(unsigned long long w) { return (w >> SB) & 1ull ? -1.0 : 1.0; }
+#else
+template <int SB> __device__ __forceinline__ double sf_sign(unsigned long long w) {
+    double sg;
+    asm volatile("s_bitcmp1_b64 %1, %2\n\ts_cselect_b64 %0, -1.0, 1.0" : "=s"(sg) : "s"(w), "n"(SB) : "scc");
+    return sg;
+}
+#endif
+// f(integral_constant<int, J>) for J = J0 .. N-1: loops whose counter is a constant expression (a bit number, a register array index)
+template <int J, int N, typename F> __device__ __forceinline__ void sf_unroll(F&& f) {
+    if constexpr (J < N) { f(std::integral_constant<int, J>{}); sf_unroll<J + 1, N>(f); }
+}
+
+// TAIL 0: |.|, 1: as it is, 2: negated
+template <int TAIL> __device__ __forceinline__ bool sf_reaches(double T, double Tid) {
+    return TAIL == 0 ? fabs(T) >= fabs(Tid) : (TAIL == 1 ? T >= Tid : T <= Tid);
+}
+
+// grid (voxel tiles, permutation chunks).  ssc = scale, negated for TAIL 2: T * -scale = -(T * scale) to the bit.
+template <int SMAX, int TAIL>
+__global__ void __launch_bounds__(SF_T)
+signflip_k(const double* __restrict__ m, const double* __restrict__ scale, sf_words signs, int S, int V, int P, int chunk,
+           double* __restrict__ part_max, int* __restrict__ part_cnt, double* __restrict__ stat0) {
+    __shared__ double tile[SF_PB * SF_PITCH];
+    const int tid = threadIdx.x;
+    const long long v = (long long)blockIdx.x * SF_T + tid;
+    const int p0 = (int)blockIdx.y * chunk, p1 = min(P, p0 + chunk);
+    const bool in = v < V;
+    const double sc = in ? scale[v] : 0.0;
+    const bool live = sc > 0.0;
+    const double ssc = TAIL == 2 ? -sc : sc;
+    double mv[SMAX];
+#pragma unroll
+    for (int s = 0; s < SMAX; ++s) { mv[s] = 0.0; if (s < S && live) mv[s] = m[(size_t)s * (size_t)V + (size_t)v]; }
+    double Tid = 0.0;                                                  // the identity, apart from the sign list
+#pragma unroll
+    for (int s = 0; s < SMAX; ++s) Tid = Tid + mv[s];
+    if (blockIdx.y == 0 && in) {
+        const double u = Tid * ssc;
+        stat0[v] = live ? (TAIL == 0 ? fabs(u) : u) : 0.0;
+    }
+    int cnt = 0;
+    for (int pb = p0; pb < p1; pb += SF_PB) {
+#pragma unroll
+        for (int q = 0; q < SF_PB; q += SF_PU) {
+            unsigned long long w[SF_PU];
+            double T[SF_PU];
+#pragma unroll
+            for (int k = 0; k < SF_PU; ++k) { w[k] = signs[min(pb + q + k, p1 - 1)]; T[k] = 0.0; }      // (behind the chunk: a word again, result dropped)
+            sf_unroll<0, SMAX / 4>([&](auto g4) {
+                constexpr int s4 = 4 * decltype(g4)::value;
+                if (s4 < S) {                                          // scalar
+                    sf_unroll<0, 4>([&](auto j) {
+                        constexpr int s = s4 + decltype(j)::value;
+#pragma unroll
+                        for (int k = 0; k < SF_PU; ++k) T[k] += sf_sign<s>(w[k]) * mv[s];
+                    });
+                }
+            });
+#pragma unroll
+            for (int k = 0; k < SF_PU; ++k) {
+                double g = T[k] * ssc;
+                if (TAIL == 0) g = fabs(g); else g = g + 0.0;          // (-0.0 -> +0.0: a zero maximum has defined bits)
+                tile[(q + k) * SF_PITCH + tid] = live ? g : SF_NEG_INF;
+                cnt += (pb + q + k < p1 && sf_reaches<TAIL>(T[k], Tid)) ? 1 : 0;
+            }
+        }
+        __syncthreads();
+        const int pr = tid >> 4, seg = tid & 15;
+        double a = SF_NEG_INF;
+#pragma unroll
+        for (int j = 0; j < 16; ++j) a = sf_max(a, tile[pr * SF_PITCH + j * 16 + seg]);
+#pragma unroll
+        for (int off = 8; off > 0; off >>= 1) a = sf_max(a, __shfl_down(a, off));
+        if (seg == 0 && pb + pr < p1) part_max[(size_t)blockIdx.x * (size_t)P + (size_t)(pb + pr)] = a;
+        __syncthreads();
+    }
+    if (in) part_cnt[(size_t)blockIdx.y * (size_t)V + (size_t)v] = cnt;   // (a voxel that takes no part: T = T_id = 0, every permutation counted)
+}
+
+// blocks [0, nbp): maxstat[p] = max over the tiles; the others: cnt_unc[v] = sum over the chunks
+__global__ void __launch_bounds__(SF_T)
+signflip_fold_k(const double* __restrict__ part_max, const int* __restrict__ part_cnt, int tiles, int chunks, int V, int P, int nbp,
+                double* __restrict__ maxstat, int* __restrict__ cnt_unc) {
+    if ((int)blockIdx.x < nbp) {
+        const int p = (int)blockIdx.x * SF_T + threadIdx.x;
+        if (p >= P) return;
+        double a = SF_NEG_INF;
+        for (int t = 0; t < tiles; ++t) a = sf_max(a, part_max[(size_t)t * (size_t)P + (size_t)p]);
+        maxstat[p] = a;
+    } else {
+        const long long v = (long long)((int)blockIdx.x - nbp) * SF_T + threadIdx.x;
+        if (v >= V) return;
+        int c = 0;
+        for (int k = 0; k < chunks; ++k) c += part_cnt[(size_t)k * (size_t)V + (size_t)v];
+        cnt_unc[v] = c;
+    }
+}
+
+// every launch decision of vg_signflip_maxstat, in the order vg_signflip_plan reports it
+struct SignflipPlan { int smax, tiles, chunk, chunks, fold_blocks; long long ws; };
+
+// 0 fine, VG_ERR_ARG, or VG_ERR_UNSUPPORTED (S > 64)
+int signflip_shape(int S, long long V, int P) {
+    if (S < 2 || V <= 0 || V >= (1LL << 31) || P <= 0 || P > (1 << 20)) return VG_ERR_ARG;
+    return S > 64 ? VG_ERR_UNSUPPORTED : VG_OK;
+}
+
+SignflipPlan signflip_plan(int S, long long V, int P) {
+    SignflipPlan p;
+    p.smax = S <= 8 ? 8 : (S <= 16 ? 16 : (S <= 32 ? 32 : 64));
+    p.tiles = (int)((V + SF_T - 1) / SF_T);
+    const int want = p.tiles >= SF_BLOCKS ? 1 : vg_cdiv(SF_BLOCKS, p.tiles);
+    p.chunk = vg_cdiv(vg_cdiv(P, want), SF_PB) * SF_PB;
+    if (p.chunk < SF_MIN_CHUNK) p.chunk = SF_MIN_CHUNK;
+    p.chunks = vg_cdiv(P, p.chunk);
+    p.fold_blocks = vg_cdiv(P, SF_T) + p.tiles;
+    p.ws = (long long)p.tiles * P * (long long)sizeof(double) + (long long)p.chunks * V * (long long)sizeof(int);
+    return p;
+}
+
 }  // namespace
 
 extern "C" int vg_pack_weights(const float* flat, float* packed, const int64_t* segs, int32_t nseg, int64_t total, void* stream) {
@@ -861,4 +1019,50 @@ extern "C" int vg_adam_step_guarded(void* p, const void* g, void* m, void* v, in
         vg_launch(adam_guarded_k<float>, dim3((unsigned)blocks), dim3(256), 0, s, (float*)p, (const float*)g, (float*)m, (float*)v,
                   (long long)n, b1, b2, eps, step_scalars, guard);
     return vg_check_launch("adam_guarded");
+}
+
+extern "C" int64_t vg_signflip_ws_bytes(int32_t S, int64_t V, int32_t P) {
+    if (signflip_shape(S, V, P)) { vg_set_error("vg_signflip_ws_bytes: bad shape (S %d, V %lld, P %d)", S, (long long)V, P); return -1; }
+    return (int64_t)signflip_plan(S, V, P).ws;
+}
+
+extern "C" int vg_signflip_plan(int32_t S, int64_t V, int32_t P, int32_t* out, int32_t n_out) {
+    if (!out || n_out < VG_SIGNFLIP_PLAN_LEN) { vg_set_error("vg_signflip_plan: out must hold %d values", VG_SIGNFLIP_PLAN_LEN); return VG_ERR_ARG; }
+    const int rc = signflip_shape(S, V, P);
+    if (rc == VG_ERR_UNSUPPORTED) { vg_set_error("vg_signflip_plan: more than 64 subjects"); return rc; }
+    if (rc) { vg_set_error("vg_signflip_plan: bad shape (S %d, V %lld, P %d)", S, (long long)V, P); return rc; }
+    const SignflipPlan p = signflip_plan(S, V, P);
+    const int v[VG_SIGNFLIP_PLAN_LEN] = {p.smax, SF_T, p.tiles, p.chunk, p.chunks, p.tiles, p.chunks, p.fold_blocks,
+                                         (int)(SF_PB * SF_PITCH * sizeof(double)), (int)(p.ws & 0x7fffffffLL), (int)(p.ws >> 31)};
+    for (int i = 0; i < VG_SIGNFLIP_PLAN_LEN; ++i) out[i] = v[i];
+    return VG_OK;
+}
+
+extern "C" int vg_signflip_maxstat(const double* m, const double* scale, const uint64_t* signs, int32_t S, int64_t V, int32_t P, int32_t tail,
+                                   void* ws, double* stat0, double* maxstat, int32_t* cnt_unc, void* stream) {
+    const int rc = signflip_shape(S, V, P);
+    if (!m || !scale || !signs || !ws || !stat0 || !maxstat || !cnt_unc || rc == VG_ERR_ARG || tail < 0 || tail > 2) {
+        vg_set_error("vg_signflip_maxstat: bad arguments S=%d V=%lld P=%d tail=%d", S, (long long)V, P, tail); return VG_ERR_ARG;
+    }
+    if (rc) { vg_set_error("vg_signflip_maxstat: more than 64 subjects"); return rc; }
+    const SignflipPlan p = signflip_plan(S, V, P);
+    double* part_max = (double*)ws;
+    int* part_cnt = (int*)(part_max + (size_t)p.tiles * (size_t)P);
+    hipStream_t s = (hipStream_t)stream;
+#define VG_SIGNFLIP(SMAX, TAIL)                                                                                                     \
+    vg_launch(signflip_k<SMAX, TAIL>, dim3(p.tiles, p.chunks), dim3(SF_T), 0, s, m, scale, (sf_words)signs, (int)S, (int)V, (int)P, \
+              p.chunk, part_max, part_cnt, stat0)
+#define VG_SIGNFLIP_T(SMAX) \
+    if (tail == 0) VG_SIGNFLIP(SMAX, 0); else if (tail == 1) VG_SIGNFLIP(SMAX, 1); else VG_SIGNFLIP(SMAX, 2)
+    if (p.smax == 8) { VG_SIGNFLIP_T(8); }
+    else if (p.smax == 16) { VG_SIGNFLIP_T(16); }
+    else if (p.smax == 32) { VG_SIGNFLIP_T(32); }
+    else { VG_SIGNFLIP_T(64); }
+#undef VG_SIGNFLIP_T
+#undef VG_SIGNFLIP
+    int lrc = vg_check_launch("signflip");
+    if (lrc) return lrc;
+    vg_launch(signflip_fold_k, dim3(p.fold_blocks), dim3(SF_T), 0, s, (const double*)part_max, (const int*)part_cnt, p.tiles, p.chunks,
+              (int)V, (int)P, vg_cdiv(P, SF_T), maxstat, cnt_unc);
+    return vg_check_launch("signflip_fold");
 }

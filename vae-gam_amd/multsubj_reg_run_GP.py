@@ -6,7 +6,8 @@ After training -- or straight from a checkpoint with `--recons_only` -- the wrap
 latent_projection.py: `<epoch>_temp.pdf` and `<epoch>_latent_projection.csv`), `model.plot_GPs` (per-covariate GP posterior
 CSVs), `recon.mk_single_volumes` (one NIfTI per volume and map) and `recon.mk_avg_maps(mk_motion_maps=True)` (subject and
 grand averages), all on the training set as the reference does.  With `--stat_maps` (an extension) `recon.mk_stat_maps` follows:
-voxel-wise standard deviations, second-level t maps and variance-explained maps in a directory of their own.
+voxel-wise standard deviations, second-level t maps and variance-explained maps in a directory of their own; `--stat_perm N` adds
+permutation p-maps of the t maps (sign flips, max-statistic) next to them.
 
 Multi-GPU: launch with torch.distributed.run, one process per GPU; the wrapper picks up RANK / LOCAL_RANK / WORLD_SIZE,
 `--batch-size` stays the GLOBAL minibatch and every rank draws its own slice of it (dp.ShardedBatchSampler); checkpoints
@@ -71,6 +72,13 @@ def build_parser():
                         help='(extension) After the averages, also write voxel-wise statistics under reconstructions/<ckpt>_stat_model_recons/: '
                              'per subject <map>_std.nii, r2.nii and <covariate map>_partial_r2.nii, at top level <map>_t.nii and r2_avg.nii '
                              '(one more pass over the training set; sums kept on the GPU).  Default: off.')
+    parser.add_argument('--stat_perm', type=int, default=0, metavar='N',
+                        help='(extension) With --stat_maps: group inference on every <map>_t.nii by a two-sided sign-flip permutation test with '
+                             'the max-statistic, N sign patterns (all 2^S of them where 2^S <= N; at most 2^20, 2 to 64 subjects): adds '
+                             '<map>_fwe_1mp.nii and <map>_unc_1mp.nii (1 - p, family-wise-error corrected and uncorrected) and '
+                             'perm_thresholds.csv.  Default 0: off.')
+    parser.add_argument('--stat_perm_seed', type=int, default=0, metavar='SEED',
+                        help='(extension) Seed of the sign patterns of --stat_perm (drawn on the CPU: the same on every device).  Default 0.')
     return parser
 
 
@@ -193,7 +201,8 @@ def export_outputs(model, loaders_dict, args, dp=None):
         recon.mk_single_volumes(loaders_dict['UnShuffled_train'], model, args.train_csv, args.save_dir)
         recon.mk_avg_maps(args.train_csv, model, args.save_dir, mk_motion_maps=True)
         if getattr(args, 'stat_maps', False):
-            recon.mk_stat_maps(args.train_csv, model, args.save_dir, loaders_dict['UnShuffled_train'], mk_motion_maps=True)
+            recon.mk_stat_maps(args.train_csv, model, args.save_dir, loaders_dict['UnShuffled_train'], mk_motion_maps=True,
+                               n_perm=getattr(args, 'stat_perm', 0), perm_seed=getattr(args, 'stat_perm_seed', 0))
     finally:
         model.dp = saved_dp
 

@@ -1157,6 +1157,39 @@ def gam_stats_accumulate(logits, gain, x, subj, acc, nat=None, grid=None, mask=N
     return acc
 
 
+SignflipPlan = namedtuple('SignflipPlan', _lib.SIGNFLIP_PLAN_FIELDS + ('ws_bytes',))
+
+
+def signflip_plan(S, V, P) -> SignflipPlan:
+    """What signflip_maxstat launches for S subjects, V voxels and P permutations, from vg_signflip_maxstat's own planner
+    (vg_signflip_plan; slot table: include/vaegam.h): nothing is launched.  ws_bytes joins the two workspace slots.  A refused shape
+    raises VgError."""
+    rec = (ctypes.c_int32 * len(_lib.SIGNFLIP_PLAN_FIELDS))()
+    _lib.get_lib().call('vg_signflip_plan', int(S), int(V), int(P), rec, len(rec))
+    return SignflipPlan(*rec, ws_bytes=int(rec[-2]) + (int(rec[-1]) << 31))
+
+
+def signflip_maxstat(m, scale, signs, tail='two'):
+    """Sign-flip permutation test with the max-statistic in one pass (vg_signflip_maxstat; the statistic to the bit: include/vaegam.h).
+    m float64 (S, V): one value per subject and voxel (subject means, or any contrast of maps), 2 <= S <= 64; scale float64 (V,):
+    1 / sqrt(S * sum_s m^2), 0 at a voxel that takes no part; signs (P,) int64 or uint64 words, bit s flips subject s; tail 'two',
+    'pos' or 'neg'.  Returns stat0 (V,) float64, maxstat (P,) float64, cnt_unc (V,) int32.  The (P, V) array of statistics is never
+    formed; no atomics: bit-reproducible."""
+    if tail not in _lib.SIGNFLIP_TAILS:
+        raise ValueError('signflip_maxstat: tail must be one of %s, not %r' % (', '.join(_lib.SIGNFLIP_TAILS), tail))
+    assert m.dim() == 2 and scale.shape == (m.shape[1],) and signs.dim() == 1 and signs.dtype in (torch.int64, torch.uint64)
+    S, V = (int(n) for n in m.shape)
+    P = int(signs.shape[0])
+    m, scale, signs = _chk(m.contiguous(), torch.float64), _chk(scale.contiguous(), torch.float64), signs.contiguous()
+    ws = torch.empty(_lib.get_lib().size('vg_signflip_ws_bytes', S, V, P), dtype=torch.uint8, device=m.device)
+    stat0 = torch.empty(V, dtype=torch.float64, device=m.device)
+    maxstat = torch.empty(P, dtype=torch.float64, device=m.device)
+    cnt = torch.empty(V, dtype=torch.int32, device=m.device)
+    _call(m, 'vg_signflip_maxstat', _p(m), _p(scale), _p(signs), S, V, P, _lib.SIGNFLIP_TAILS.index(tail), _p(ws), _p(stat0), _p(maxstat),
+          _p(cnt))
+    return stat0, maxstat, cnt
+
+
 class CholeskyF64(torch.autograd.Function):
     """L = chol(A) for a batch of small float64 SPD matrices (vg_cholesky_f64; n <= 128).  Backward is the
     standard  dA = sym( L^-T  Phi(L^T dL)  L^-1 )  with two triangular solves (rocBLAS trsm, capturable)."""
